@@ -6,7 +6,19 @@ CLAHE autoscale to u8, then suppressed synthetic-RGB composition) over one synth
 20000 x 20000 dual-pol u16 scene that is already resident in HBM.  Output: the interleaved
 RGB raster in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode batch|stripe]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode batch|stripe] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline needs and nothing else: it makes the resident scenes, warms up, times the K steps (one HIP event
+pair per step, on the dominant kernel, for the roofline fraction), writes the last step's raster if --dump-outputs is given, and
+prints the line.  --full adds everything that is measured or checked BESIDE the headline, each with runs of its own: one synchronous
+call per scene, the one-stream and scene-A loops, the per-kernel breakdown, the CPU baseline with the full-size parity check, the
+secondary records (N = 1: a child process; N > 1: row-stripe and PCIe legs on all ranks) and roofline.traffic under rocprofv3
+(--no-cpu-baseline, --no-cpu-full, --no-secondary, --no-traffic take single parts out of a --full run again).
+
+--dump-outputs DIR writes what the last timed step computed -- the interleaved RGB raster a caller of the timed entry point receives --
+as DIR/rgb.npy (float32; a raster above 48 MB as float32 is sampled: as many whole rows as fit, drawn with a fixed seed, their indices
+in DIR/rgb_rows.npy) and the per-channel level histogram of the WHOLE raster as DIR/rgb_hist.npy (float64, 3 x 256).  The scenes come from
+fixed seeds: two runs with the same arguments see the same inputs.
 
 N > 1 runs one rank per GPU under torch.distributed.run.  Started WITHOUT that launcher (`python bench.py --gpus N`) the
 script starts it itself, as a child process and before anything touches a GPU, and relays rank 0's JSON line and the
@@ -18,7 +30,7 @@ child's exit code.  Modes:
 
 Prints ONE JSON line on rank 0 (see the task contract), including
   roofline     -- dominant kernel, algorithmic bytes / HIP-event time vs 8 TB/s HBM peak
-  cpu_baseline -- the CPU oracle (single thread, = the reference's behaviour) on a bounded
+  cpu_baseline -- (--full) the CPU oracle (single thread, = the reference's behaviour) on a bounded
                   sample of the same workload, timed on this box's host cores (N=1 only)
 """
 from __future__ import annotations
@@ -46,6 +58,9 @@ def main():
     ap.add_argument("--rows", type=int, default=20000)
     ap.add_argument("--cols", type=int, default=20000)
     ap.add_argument("--strategy", default="clahe")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beside the headline (per-scene and one-stream loops, per-kernel breakdown, CPU baseline "
+                                                        "with the full-size parity check, secondary records, live roofline.traffic): minutes instead of seconds")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's RGB raster (sampled rows above 48 MB) and its level histogram as DIR/*.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--sync-steps", action="store_true", help="one host round trip per scene instead of stream-ordered enqueue")
     ap.add_argument("--cpu-sample", type=int, default=7000, help="side of the square CPU-baseline sample scene (median of 3 runs)")
@@ -71,10 +86,10 @@ def main():
         sys.exit(traffic_child(args))
     # N = 1: the secondary records are measured by a CHILD process, started here -- before this process touches a GPU runtime --
     # and parked on its stdin until the headline is done (see secondary_start)
-    sec_child = secondary_start(args) if (args.gpus == 1 and not args.no_secondary) else None
+    sec_child = secondary_start(args) if (args.full and args.gpus == 1 and not args.no_secondary) else None
     # roofline.traffic is MEASURED by this run: a second child, parked like the first, runs the headline scene under
     # rocprofv3 --pmc (FETCH_SIZE and WRITE_SIZE in separate passes) once the timed region is over
-    traffic_proc = traffic_start(args) if (args.gpus == 1 and not args.no_traffic and args.strategy.lower() == "clahe"
+    traffic_proc = traffic_start(args) if (args.full and args.gpus == 1 and not args.no_traffic and args.strategy.lower() == "clahe"
                                            and (args.rows, args.cols) == (20000, 20000)) else None
 
     import torch
@@ -177,16 +192,17 @@ def main():
     for i in range(K):
         step(i)  # (first touch of this scene's rasters: the second call is the one that is timed -- a cold call read 1.19-1.46 ms where the cycle shows 1.05)
         ctx.synchronize()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        step(i)
-        ctx.synchronize()
-        scene_sync_ms.append((time.perf_counter() - t0) * 1e3)
+        if args.full:  # (a plain run keeps the first touch, which is warm-up, and the route, which the roofline average needs)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            step(i)
+            ctx.synchronize()
+            scene_sync_ms.append((time.perf_counter() - t0) * 1e3)
         try:
             outcomes.append(ctx.spec_report()["outcome"] if (strategy == AutoscaleStrategy.Clahe and not striped) else "n/a")
         except Exception:
             outcomes.append("n/a")  # (no speculative chain ran: a scene below the route's size threshold)
-        if i == 0 and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.no_cpu_full and not striped:
+        if args.full and i == 0 and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.no_cpu_full and not striped:
             rgb_a_host = rgb.view(max(rows_local, 1), pitch, 3)[:, :cols].cpu().numpy()
     wtimes: dict[str, float] = {}
     for w in range(args.warmup):
@@ -238,6 +254,8 @@ def main():
     if K > 1 and len(dtimes) == args.steps and dom_warm == "clahe_rgb_fused":
         rts = routes_timed if routes_timed is not None else [outcomes[i % K] for i in range(args.steps)]
         dtimes = [ms for i, ms in enumerate(dtimes) if rts[i] in ("accepted", "retried", "refuted")]
+    if args.dump_outputs and args.steps > 0:  # before anything else writes a raster: the last timed step's (pipelined: scene i -> rgbs[i mod lanes])
+        dump_outputs(torch, args.dump_outputs, rgbs[(args.steps - 1) % len(rgbs)], rows_local, cols, pitch, rank)
 
     subset_dom_ms: list[float] = []  # the dominant kernel's event times of the LAST timed_subset run (one stream: nothing beside the kernel)
     subset_dom_scene: list[int] = []  # ... and the scene of each
@@ -258,9 +276,9 @@ def main():
                 subset_dom_ms[:] = [kt[i] for i in keep]
                 subset_dom_scene[:] = [idx[i % len(idx)] for i in keep]
         return sorted(runs)[1]
-    ms_accepted = timed_subset([i for i in range(K) if outcomes[i] in ("accepted", "n/a")]) if K > 1 else None
-    ms_scene_a = timed_subset([0]) if (K > 1 or pipelined) else None
-    ms_one_stream = timed_subset(list(range(K))) if pipelined else None  # the whole cycle, one call per scene on one stream (the headline loop of rounds 3-4)
+    ms_accepted = timed_subset([i for i in range(K) if outcomes[i] in ("accepted", "n/a")]) if (args.full and K > 1) else None
+    ms_scene_a = timed_subset([0]) if (args.full and (K > 1 or pipelined)) else None
+    ms_one_stream = timed_subset(list(range(K))) if (args.full and pipelined) else None  # the whole cycle, one call per scene on one stream (the headline loop of rounds 3-4)
     # Under the lanes a kernel's event pair brackets more than the kernel when another lane's sweep shares the chip (round 5's free
     # run: its workgroups are dispatched as the other sweep releases compute units).  `roofline.frac` / `achieved` / `ms_per_launch`
     # are the figures of the TIMED REGION, whatever they bracket; the same kernel on the one-stream cycle measured right after it
@@ -272,7 +290,7 @@ def main():
         per_scene_ms.setdefault(sc_i, []).append(ms)
     ctx.time_only(None)
     ktimes: dict[str, list[float]] = {}
-    for _ in range(EXTRA_STEPS):  # (scene A: the per-kernel breakdown of the route that is taken when the speculation holds)
+    for _ in range(EXTRA_STEPS if args.full else 0):  # (scene A: the per-kernel breakdown of the route that is taken when the speculation holds)
         step(0)
         ctx.synchronize()
         for name, ms in ctx.last_kernel_times():
@@ -292,7 +310,7 @@ def main():
         launches = {k: len(v) / EXTRA_STEPS for k, v in ktimes.items()}
         total_ms = {k: per_launch[k] * launches[k] for k in per_launch}
         kern = {k: v for k, v in total_ms.items() if not k.startswith("host:")}  # host:* entries are wall-clock segments
-        dom = dom_warm if dom_warm in kern else (max(kern, key=kern.get) if kern else None)
+        dom = dom_warm if (dom_warm in kern or (dtimes and not args.full)) else (max(kern, key=kern.get) if kern else None)  # (plain run: no extra steps, the timed region's events alone)
         if dom == dom_warm and dtimes:  # the roofline figure is the one measured inside the timed region
             per_launch[dom] = float(np.mean(dtimes))
             launches[dom] = len(dtimes) / args.steps
@@ -319,6 +337,8 @@ def main():
                         "timed_in": "timed region (HIP events on this kernel only, on the stream it is launched on)" if (dom == dom_warm and dtimes) else "extra steps",
                         "kernels_ms_per_step": {k: round(total_ms[k], 4) for k in sorted(total_ms)},
                         "kernels_ms_per_step_from": f"{EXTRA_STEPS} fully instrumented steps after the timed region"}
+            if not args.full:  # the per-kernel breakdown takes fully instrumented steps of its own
+                del roofline["kernels_ms_per_step"], roofline["kernels_ms_per_step_from"]
             if one_stream_ms:
                 m1 = float(np.mean(one_stream_ms))
                 roofline["ms_per_launch_one_stream"] = round(m1, 4)
@@ -334,7 +354,7 @@ def main():
             "value": round(value, 1), "unit": "Mpix/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True,
             "scaling": "strong" if (args.mode == "stripe" and world > 1) else "weak",
-            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "vs_baseline": None, "dtype": "f64", "data": "synthetic", "full": args.full,
             "config": {"workload": f"{rows}x{cols} dual-pol u16 in HBM -> dB+{strategy.name} u8 x2 -> synRGB u8, native res (save.rs:317-367)",
                        "workload_detail": f"dual-pol u16 {rows}x{cols} scene resident in HBM -> dB + {strategy.name} autoscale u8 x2 "
                                           f"-> synRGB ({'suppressed' if strategy.name in ('Clahe', 'Tamed') else 'default'} variant) interleaved u8, native resolution (save.rs:317-367); "
@@ -343,7 +363,8 @@ def main():
                        "scenes_in_cycle": K,
                        "mode": args.mode if world > 1 else "single", "rows": rows, "cols": cols,
                        "scenes_per_step": scenes_per_step,
-                       "scenes": [{"name": d[0], "what": d[4], "route": outcomes[i], "ms_one_synchronous_call": round(scene_sync_ms[i], 3)} for i, d in enumerate(scene_defs)],
+                       "scenes": [dict({"name": d[0], "what": d[4], "route": outcomes[i]}, **({"ms_one_synchronous_call": round(scene_sync_ms[i], 3)} if args.full else {}))
+                                  for i, d in enumerate(scene_defs)],
                        "warmup_through_lanes": warm_pipelined,
                        "enqueue": (f"resident batch entry point (sarpro_hip_batch_dualpol_synrgb_u16_dev), {len(rgbs)} internal lanes, ONE call for the {args.steps} timed steps, "
                                    "synchronous (returns when every raster is complete)") if pipelined
@@ -357,8 +378,9 @@ def main():
             # three the exact apply -> finish -> compose kernels produced the raster (inside `value`)
             per_step = routes_timed if routes_timed is not None else [outcomes[i % K] for i in range(args.steps)]  # pipelined: what the batch reported per scene
             out["spec"] = {k: per_step.count(k) for k in ("accepted", "retried", "refuted", "unproven", "pool_overflow")}
-            out["ms_per_step_accepted_scenes"] = round(ms_accepted, 3) if ms_accepted is not None else out["ms_per_step"]
-            out["ms_per_step_scene_a"] = round(ms_scene_a, 3) if ms_scene_a is not None else out["ms_per_step"]
+            if args.full:
+                out["ms_per_step_accepted_scenes"] = round(ms_accepted, 3) if ms_accepted is not None else out["ms_per_step"]
+                out["ms_per_step_scene_a"] = round(ms_scene_a, 3) if ms_scene_a is not None else out["ms_per_step"]
             if ms_one_stream is not None:
                 out["ms_per_step_one_stream"] = round(ms_one_stream, 3)
                 out["ms_per_step_note"] = ("ms_per_step / value: the resident batch entry point (lanes overlap the scenes' chains); ms_per_step_one_stream: the same nine-scene cycle, "
@@ -369,12 +391,12 @@ def main():
     # failure in it costs its own record, never the line
     # one rank, one whole scene A (batch mode): the N = 1 reference of the stripe leg, which runs scene A
     single_ms = ms_scene_a if ms_scene_a is not None else elapsed / args.steps * 1e3
-    if rank == 0:  # the measured headline, on stderr, BEFORE anything beside it runs: a hang or a kill further down still leaves it in the log
+    if rank == 0 and args.full:  # the measured headline, on stderr, BEFORE anything beside it runs: a hang or a kill further down still leaves it in the log
         print("bench.py headline (the full record follows on stdout): " + json.dumps({k: out[k] for k in ("metric", "value", "unit", "n_gpus", "ms_per_step")}),
               file=sys.stderr, flush=True)
     del band, rgb, rgbs, scenes
     torch.cuda.empty_cache()
-    if world > 1 and not args.no_secondary:
+    if args.full and world > 1 and not args.no_secondary:
         sec = {}
         try:
             sec = multi_rank_records(torch, dist, dev, rank, world, rows, cols, strategy, single_ms if args.mode == "batch" else None)
@@ -383,7 +405,7 @@ def main():
         if rank == 0:
             out["secondary"] = sec
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(ctx, q, args.cpu_sample, int(strategy), torch, dev, rows if not args.no_cpu_full else 0, cols, rgb_a_host)
             except Exception as e:
@@ -417,6 +439,34 @@ def main():
         dist.destroy_process_group()
     if parity_failed:  # the line is out (a reader sees the flag); the exit code says the same
         sys.exit("bench.py: the GPU's RGB raster of scene A differs from the CPU oracle's at full size")
+
+
+DUMP_MAX_BYTES = 48 << 20  # of rgb.npy; with the histogram and the row indices a dump stays well below 64 MB
+DUMP_SEED = 0x5A12
+
+
+def dump_outputs(torch, d, rgb, rows_local, cols, pitch, rank):
+    """--dump-outputs: the raster of the last timed step as the caller sees it (rows_local x cols x 3, the pad columns of the pitch cut
+    off), float32.  A raster above DUMP_MAX_BYTES is sampled: as many whole rows as fit, drawn without replacement by a generator seeded
+    with DUMP_SEED (the same rows in every run of the same shape), in ascending order, their indices beside them.  The per-channel level
+    histogram covers EVERY pixel, so a difference outside the sampled rows still shows.  Rank r > 0 writes <name>.rank<r>.npy."""
+    os.makedirs(d, exist_ok=True)
+    sfx = "" if rank == 0 else f".rank{rank}"
+    img = rgb.view(-1, pitch, 3)[:rows_local, :cols]
+    off = torch.arange(3, dtype=torch.int64, device=rgb.device) * 256
+    hist = torch.zeros(768, dtype=torch.int64, device=rgb.device)
+    for r in range(0, rows_local, 512):
+        hist += torch.bincount((img[r:r + 512].to(torch.int64) + off).reshape(-1), minlength=768)
+    np.save(os.path.join(d, f"rgb_hist{sfx}.npy"), hist.view(3, 256).cpu().numpy().astype(np.float64))
+    fit = max(1, DUMP_MAX_BYTES // (cols * 3 * 4))
+    if fit >= rows_local:
+        pick = np.arange(rows_local)
+        sample = img
+    else:
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(rows_local, size=fit, replace=False))
+        sample = img[torch.as_tensor(pick, device=rgb.device)]
+    np.save(os.path.join(d, f"rgb{sfx}.npy"), sample.to(torch.float32).cpu().numpy())
+    np.save(os.path.join(d, f"rgb_rows{sfx}.npy"), pick.astype(np.float64))
 
 
 def self_launch(args):

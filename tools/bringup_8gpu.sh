@@ -28,7 +28,7 @@ for n in 2 $N; do PORT=$((PORT + 1)); run stripes_$n $(launch $n) tools/bringup_
 run multi_worker python -m pytest tests/test_gpu_multi_worker.py -x -q -m gpu
 for n in 2 4 $N; do
   [ $n -gt $N ] && continue
-  run bench_batch_$n python bench.py --gpus $n --steps 10 --warmup 3 --mode batch
-  run bench_stripe_$n python bench.py --gpus $n --steps 10 --warmup 3 --mode stripe
+  run bench_batch_$n python bench.py --gpus $n --steps 10 --warmup 3 --mode batch --full
+  run bench_stripe_$n python bench.py --gpus $n --steps 10 --warmup 3 --mode stripe --full
 done
 [ $DRY = 1 ] || { echo "bring-up passed on $N GPUs; bench lines:"; grep -h '^{' $OUT/bench_*.log | cut -c1-400; }

@@ -4,9 +4,9 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r3; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 # 1. the driver's command under rocprofv3 --kernel-trace --stats: default route (fused CLAHE -> RGB pass), then the apply + compose route
-rocprofv3 --kernel-trace --stats -d $O/bench_stats -o bench --output-format csv -- python3 $R/bench.py --no-secondary --no-cpu-baseline > $O/bench_line_under_rocprof.json 2> $O/bench_stats.log
+rocprofv3 --kernel-trace --stats -d $O/bench_stats -o bench --output-format csv -- python3 $R/bench.py --full --no-secondary --no-cpu-baseline > $O/bench_line_under_rocprof.json 2> $O/bench_stats.log
 export SARPRO_HIP_NO_FUSED_RGB=1
-rocprofv3 --kernel-trace --stats -d $O/bench_apply_compose_stats -o bench --output-format csv -- python3 $R/bench.py --no-secondary --no-cpu-baseline > $O/bench_apply_compose_line_under_rocprof.json 2> $O/bench_apply_compose_stats.log
+rocprofv3 --kernel-trace --stats -d $O/bench_apply_compose_stats -o bench --output-format csv -- python3 $R/bench.py --full --no-secondary --no-cpu-baseline > $O/bench_apply_compose_line_under_rocprof.json 2> $O/bench_apply_compose_stats.log
 unset SARPRO_HIP_NO_FUSED_RGB
 # 2. HBM traffic (FETCH_SIZE / WRITE_SIZE, separate passes) of both routes' kernels; SQ counters of the fused pass and of the apply pass
 bash $R/tools/pmc_traffic.sh $O/pmc_traffic > $O/pmc_traffic.txt 2>&1
@@ -16,7 +16,7 @@ SARPRO_HIP_NO_FUSED_RGB=1 PMC_KERNEL=k_clahe_apply_u8_spec bash $R/tools/pmc_app
 SARPRO_HIP_NO_FUSED_RGB=1 SARPRO_HIP_STRIP_ALIGN=8 SARPRO_HIP_NO_SAMPLED_HIST=1 SARPRO_HIP_CHUNK_ROWS=234 PMC_KERNEL=k_clahe_apply_u8_spec bash $R/tools/pmc_apply.sh $O/pmc_apply_r2_form > $O/pmc_apply_r2_form.txt 2>&1
 cd $R
 # 3. the bench line as the driver runs it (secondary records, full-size CPU baseline)
-python3 bench.py > $O/bench_full.json 2> $O/bench_full.log
+python3 bench.py --full > $O/bench_full.json 2> $O/bench_full.log
 # 4. the tools behind the prose figures
 python3 tools/time_variants.py - -:SARPRO_HIP_NO_FUSED_RGB=1 -:SARPRO_HIP_NO_FUSED_RGB=1,SARPRO_HIP_NO_SAMPLED_HIST=1 -:SARPRO_HIP_NO_FUSED_RGB=1,SARPRO_HIP_NO_SAMPLED_HIST=1,SARPRO_HIP_STRIP_ALIGN=8,SARPRO_HIP_CHUNK_ROWS=234 - > $O/time_routes.txt 2>&1
 python3 tools/time_resize_flow.py > $O/time_resize_flow.txt 2>&1

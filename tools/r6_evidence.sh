@@ -5,8 +5,8 @@ set -u
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r6e_evidence; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 # 1. the driver's command under rocprofv3 --kernel-trace --stats (resident batch over the nine-scene cycle), and the one-stream loop (--lanes 0)
-rocprofv3 --kernel-trace --stats -d $O/bench_stats -o bench --output-format csv -- python3 $R/bench.py --no-secondary --no-cpu-baseline --no-traffic > $O/bench_line_under_rocprof.json 2> $O/bench_stats.log
-rocprofv3 --kernel-trace --stats -d $O/bench_one_stream_stats -o bench --output-format csv -- python3 $R/bench.py --no-secondary --no-cpu-baseline --no-traffic --lanes 0 > $O/bench_one_stream_line_under_rocprof.json 2> $O/bench_one_stream_stats.log
+rocprofv3 --kernel-trace --stats -d $O/bench_stats -o bench --output-format csv -- python3 $R/bench.py --full --no-secondary --no-cpu-baseline --no-traffic > $O/bench_line_under_rocprof.json 2> $O/bench_stats.log
+rocprofv3 --kernel-trace --stats -d $O/bench_one_stream_stats -o bench --output-format csv -- python3 $R/bench.py --full --no-secondary --no-cpu-baseline --no-traffic --lanes 0 > $O/bench_one_stream_line_under_rocprof.json 2> $O/bench_one_stream_stats.log
 # 2. the lanes' timeline: kernel trace of one resident batch, overlap per sweep
 rocprofv3 --kernel-trace -d $O/pipe_trace -o pipe --output-format csv -- python3 $R/tools/pipe_trace.py 6 > $O/pipe_trace.log 2>&1
 python3 $R/tools/trace_overlap.py $O/pipe_trace 6 > $O/pipe_trace_overlap.txt 2>&1
@@ -21,7 +21,7 @@ rocprofv3 --kernel-trace --stats -d $O/config2_stats -o c2 --output-format csv -
 rocprofv3 --kernel-trace --stats -d $O/config3_stats -o c3 --output-format csv -- python3 $R/tools/trace_f32.py > $O/config3_stats.log 2>&1
 cd $R
 # 5. the bench line as the driver runs it (secondary records, full-size CPU baseline, live PMC traffic)
-python3 bench.py > $O/bench_full.json 2> $O/bench_full.log
+python3 bench.py --full > $O/bench_full.json 2> $O/bench_full.log
 # 6. the tools behind the prose figures
 python3 tools/time_scenes.py > $O/time_scenes.txt 2>&1
 REPS=4 CONFIGS=3:0:0:0,3:3:0:0,2:3:0:0,3:1:0:0,3:0:0:0,3:3:0:0 python3 tools/pipe_sweep.py > $O/pipe_sweep.txt 2>&1
