@@ -50,6 +50,7 @@ extern "C" {
 #define SARPRO_HIP_ERR_OOM (-6)
 #define SARPRO_HIP_ERR_NO_DEVICE (-7)
 #define SARPRO_HIP_ERR_IO (-8) /* a row reader / sink / TIFF file failed */
+#define SARPRO_HIP_ERR_BUFFER_TOO_SMALL (-9) /* an output buffer's capacity: the call reports the size it needs */
 
 /* ---- src/types.rs discriminants ---- */
 typedef enum { /* types.rs:115-123 */
@@ -219,6 +220,41 @@ int sarpro_hip_dualpol_synrgb_resized_f32_dev(sarpro_hip_ctx *ctx, const float *
 int sarpro_hip_dualpol_synrgb_resized_u16_dev(sarpro_hip_ctx *ctx, const uint16_t *d_band1, const uint16_t *d_band2, size_t rows,
                                               size_t cols, size_t in_pitch, int strategy, int mode, size_t target_size, int pad,
                                               uint8_t *d_rgb_out, sarpro_hip_resize_meta *meta);
+
+/* ================= JPEG encoding (io/writers/jpeg.rs:14,27 write_rgb_jpeg / write_gray_jpeg) =================
+ * What the reference's JPEG branches end in (save.rs:317-403, api/mod.rs:404-437): jpeg_encoder::Encoder::new(w, 100).  Baseline
+ * sequential JPEG, quality 100 (not a parameter: every quantisation entry is 1), all sampling factors 1x1 (the crate's choice for
+ * quality >= 90), the Annex K Huffman tables (not optimised), components = 1 (gray) or 3 (RGB -> YCbCr).  The arithmetic is libjpeg's:
+ * jccolor with 16 fractional bits, edge blocks replicating the last column and row, jfdctint ("islow"), divisor 8, jchuff's coding.
+ * The scan carries restart intervals (a DRI segment with the interval, RST0..7 markers): the segments are independent, which is what
+ * the device parallelises over; any decoder reads such a file.  restart_mcus = 0 picks the library's interval (DESIGN.md "JPEG
+ * encoding"), 1..65535 are taken as given.  cols and rows must be 1..65535 (the reference's `as u16` cast truncates silently: refused
+ * here), components 1 or 3: SARPRO_HIP_ERR_INVALID_ARG otherwise.  File layout: SOI, APP0 JFIF 1.01, DQT, SOF0, DHT, DRI, SOS, scan,
+ * EOI.  The scan is checked byte for byte against libjpeg-turbo; parity with the jpeg-encoder crate itself is unpinned (crate source
+ * absent, version not locked): it is documented as a port of the same libjpeg jfdctint and colour arithmetic. */
+/* Everything up to and including the SOS header (no GPU): *bytes = its length; SARPRO_HIP_ERR_BUFFER_TOO_SMALL when cap is less. */
+int sarpro_hip_host_jpeg_header(size_t cols, size_t rows, int components, unsigned restart_mcus, uint8_t *out, size_t cap, size_t *bytes);
+/* A capacity no file of this shape can exceed (no GPU): the longest codes of the four tables, the category limits of 8-bit input,
+ * every byte stuffed.  Far above real files (about 6.5 bytes per sample): a caller may offer less and retry with the size the
+ * encoder reports. */
+int sarpro_hip_jpeg_bound(size_t cols, size_t rows, int components, unsigned restart_mcus, size_t *bytes);
+/* The raster (pitch_bytes per row: interleaved RGB or a gray plane) and the file both in device memory.  Synchronous: one
+ * synchronisation, the one that returns *bytes_out.  When the file does not fit, nothing at or past out_capacity is written, *bytes_out
+ * is the size it needs and the status is SARPRO_HIP_ERR_BUFFER_TOO_SMALL.  Kernel times: jpeg_transform, jpeg_entropy_size, jpeg_scan,
+ * jpeg_entropy_write. */
+int sarpro_hip_jpeg_encode_dev(sarpro_hip_ctx *ctx, const uint8_t *d_pixels, size_t cols, size_t rows, size_t pitch_bytes, int components,
+                               unsigned restart_mcus, uint8_t *d_out, size_t out_capacity, size_t *bytes_out);
+/* The raster and the file both in host memory: the raster goes up, only the file comes back. */
+int sarpro_hip_jpeg_encode(sarpro_hip_ctx *ctx, const uint8_t *pixels, size_t cols, size_t rows, size_t pitch_bytes, int components,
+                           unsigned restart_mcus, uint8_t *out, size_t out_capacity, size_t *bytes_out);
+/* sarpro_hip_dualpol_synrgb_resized_u16 / _f32 up to the FILE the reference writes: the device-resident flow composes the RGB raster
+ * into a raster of the context and the encoder reads it there; the raster never leaves the device, only the file crosses PCIe. */
+int sarpro_hip_dualpol_synrgb_resized_u16_jpeg(sarpro_hip_ctx *ctx, const uint16_t *band1, const uint16_t *band2, size_t rows, size_t cols,
+                                               int strategy, int mode, size_t target_size, int pad, uint8_t *jpeg_out, size_t jpeg_capacity,
+                                               size_t *jpeg_bytes_out, unsigned restart_mcus, sarpro_hip_resize_meta *meta);
+int sarpro_hip_dualpol_synrgb_resized_f32_jpeg(sarpro_hip_ctx *ctx, const float *band1, const float *band2, size_t rows, size_t cols, int strategy,
+                                               int mode, unsigned flags, size_t target_size, int pad, uint8_t *jpeg_out, size_t jpeg_capacity,
+                                               size_t *jpeg_bytes_out, unsigned restart_mcus, sarpro_hip_resize_meta *meta);
 
 /* save_processed_image (save.rs:23-170) up to the raster its writer receives: pipeline at native
  * resolution -> resize -> pad, on the device.  `out` holds final_rows * final_cols u8 / u16 elements.

@@ -737,7 +737,43 @@ pub fn render_multiband_image(processed1: &Array2<f32>, processed2: &Array2<f32>
     with_core(|c| c.try_render_multiband_image(processed1, processed2, format, bit_depth, target_size, pad, autoscale, syn_mode))
 }
 
-/// The encoders stay sarpro's (io/writers/*: GDAL GeoTIFF, JPEG + sidecars): implement this for them.  `metadata` is the
+impl RasterCore {
+    /// io/writers/jpeg.rs:14,27 on the device: `data` is `height` rows of `width` pixels, interleaved RGB (`components` = 3) or
+    /// gray (1) -> the JPEG file (baseline, quality 100, 4:4:4, as `jpeg_encoder::Encoder::new(w, 100)` writes it, with restart
+    /// intervals of `restart_mcus` MCUs; 0 = the library's).  The raster goes up, only the file comes back.
+    pub fn try_encode_jpeg(&self, data: &[u8], width: usize, height: usize, components: usize, restart_mcus: u32) -> Result<Vec<u8>> {
+        if data.len() != width * height * components {
+            return Err(HipError { code: sys::SARPRO_HIP_ERR_SHAPE_MISMATCH, message: "raster length is not width * height * components".into() });
+        }
+        let mut bound = 0usize;
+        self.chk(unsafe { sys::sarpro_hip_jpeg_bound(width, height, components as c_int, restart_mcus as c_uint, &mut bound) })?;
+        // the bound is far above real files: offer three times the raster first, then what the encoder asks for
+        let mut cap = bound.min((3 * data.len()).max(1 << 16));
+        loop {
+            let mut out = vec![0u8; cap];
+            let mut n = 0usize;
+            let rc = unsafe { sys::sarpro_hip_jpeg_encode(self.ctx, data.as_ptr(), width, height, width * components, components as c_int,
+                restart_mcus as c_uint, out.as_mut_ptr(), cap, &mut n) };
+            if rc == sys::SARPRO_HIP_ERR_BUFFER_TOO_SMALL && n > cap { cap = n; continue; }
+            self.chk(rc)?;
+            out.truncate(n);
+            return Ok(out);
+        }
+    }
+}
+
+/// `write_rgb_jpeg` (io/writers/jpeg.rs:14) up to the bytes of the file: the device replacement of its `jpeg_encoder` call.
+pub fn encode_jpeg_rgb(rgb: &[u8], width: usize, height: usize) -> Result<Vec<u8>> {
+    with_core(|c| c.try_encode_jpeg(rgb, width, height, 3, 0))
+}
+
+/// `write_gray_jpeg` (io/writers/jpeg.rs:27) up to the bytes of the file.
+pub fn encode_jpeg_gray(gray: &[u8], width: usize, height: usize) -> Result<Vec<u8>> {
+    with_core(|c| c.try_encode_jpeg(gray, width, height, 1, 0))
+}
+
+/// The encoders stay sarpro's (io/writers/*: GDAL GeoTIFF, JPEG + sidecars; for the JPEG bytes themselves there is
+/// [`encode_jpeg_rgb`] / [`encode_jpeg_gray`]): implement this for them.  `metadata` is the
 /// caller's `SafeMetadata`, passed through untouched; `operation` carries the label save.rs:34-47 embeds.
 pub trait RasterWriter<M: ?Sized> {
     fn write(&mut self, output: &Path, image: &ProcessedImage, metadata: Option<&M>, operation: ProcessingOperation)

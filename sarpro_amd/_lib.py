@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("SARPRO_HIP_LIB") or os.path.join(_HERE, "libsarpro_hi
 OK = 0
 ERR_INVALID_ARG, ERR_SHAPE_MISMATCH, ERR_UNSUPPORTED_SHAPE = -1, -2, -3
 ERR_HIP, ERR_RCCL, ERR_OOM, ERR_NO_DEVICE, ERR_IO = -4, -5, -6, -7, -8
+ERR_BUFFER_TOO_SMALL = -9
 
 
 class Stats(C.Structure):
@@ -108,6 +109,8 @@ SYMBOLS = [
     "sarpro_hip_batch_dualpol_synrgb_resized_u16", "sarpro_hip_batch_dualpol_synrgb_u16_dev", "sarpro_hip_batch_dualpol_synrgb_resized_f32_dev",
     "sarpro_hip_synth_scene_u16_dev", "sarpro_hip_synth_scene_u16_dev_ex",
     "sarpro_hip_local_group_create", "sarpro_hip_local_group_destroy", "sarpro_hip_comm_init_local", "sarpro_hip_host_clahe_saturated_levels", "sarpro_hip_ctx_set_attr", "sarpro_hip_ctx_reset_attr", "sarpro_hip_ctx_get_attr", "sarpro_hip_attr_name",
+    "sarpro_hip_host_jpeg_header", "sarpro_hip_jpeg_bound", "sarpro_hip_jpeg_encode_dev", "sarpro_hip_jpeg_encode",
+    "sarpro_hip_dualpol_synrgb_resized_u16_jpeg", "sarpro_hip_dualpol_synrgb_resized_f32_jpeg",
 ]
 
 if not os.path.exists(LIB_PATH):
@@ -273,3 +276,9 @@ _proto("sarpro_hip_tiff_finish", _i, _vp)
 _proto("sarpro_hip_tiff_last_error", C.c_char_p)
 _proto("sarpro_hip_host_update_geotransform", None, _vp, _sz, _sz, _M)
 _proto("sarpro_hip_dualpol_synrgb_resized_stream_u16", _i, _vp, _vp, _vp, _sz, _sz, _i, _i, _sz, _i, _vp, _M)
+_proto("sarpro_hip_host_jpeg_header", _i, _sz, _sz, _i, _u, _vp, _sz, C.POINTER(_sz))
+_proto("sarpro_hip_jpeg_bound", _i, _sz, _sz, _i, _u, C.POINTER(_sz))
+_proto("sarpro_hip_jpeg_encode_dev", _i, _vp, _vp, _sz, _sz, _sz, _i, _u, _vp, _sz, C.POINTER(_sz))
+_proto("sarpro_hip_jpeg_encode", _i, _vp, _vp, _sz, _sz, _sz, _i, _u, _vp, _sz, C.POINTER(_sz))
+_proto("sarpro_hip_dualpol_synrgb_resized_u16_jpeg", _i, _vp, _vp, _vp, _sz, _sz, _i, _i, _sz, _i, _vp, _sz, C.POINTER(_sz), _u, _M)
+_proto("sarpro_hip_dualpol_synrgb_resized_f32_jpeg", _i, _vp, _vp, _vp, _sz, _sz, _i, _i, _u, _sz, _i, _vp, _sz, C.POINTER(_sz), _u, _M)

@@ -362,6 +362,76 @@ class Context:
                                                                 1 if plain_pipeline else 0, target_size or 0, int(pad), _vp(d_rgb), C.byref(m)))
         return m
 
+    # ------------------------------------------------------------------ io/writers/jpeg.rs:14,27
+    def _jpeg_call(self, fn, n_raster_bytes: int, bound: int):
+        """fn(buffer, capacity, byref(bytes)) -> status, with a buffer that grows to the size the encoder reports."""
+        cap = min(bound, max(1 << 16, 3 * n_raster_bytes))
+        while True:
+            buf = np.empty(cap, np.uint8)
+            n = C.c_size_t(0)
+            rc = fn(_vp(buf), cap, C.byref(n))
+            if rc == _lib.ERR_BUFFER_TOO_SMALL and n.value > cap:
+                cap = n.value
+                continue
+            self._chk(rc)
+            return buf[:n.value].tobytes()
+
+    def jpeg_encode(self, array: np.ndarray, restart_mcus: int = 0) -> bytes:
+        """write_rgb_jpeg / write_gray_jpeg: a (rows, cols, 3) RGB or (rows, cols) gray uint8 raster -> the JPEG file (quality 100,
+        4:4:4, restart interval `restart_mcus` MCUs, 0 = the library's).  Rows may be pitched (a view of a wider array)."""
+        if array.dtype != np.uint8 or array.ndim not in (2, 3) or (array.ndim == 3 and array.shape[2] != 3):
+            raise ValueError("array must be a (rows, cols) or (rows, cols, 3) uint8 raster")
+        nc = 1 if array.ndim == 2 else 3
+        rows, cols = array.shape[:2]
+        if rows and cols and (array.strides[-1] != 1 or (nc == 3 and array.strides[1] != 3) or array.strides[0] < cols * nc):
+            array = np.ascontiguousarray(array)
+        pitch = array.strides[0] if rows and cols else cols * nc
+        bound = jpeg_bound(cols, rows, nc, restart_mcus)
+        return self._jpeg_call(lambda out, cap, n: lib.sarpro_hip_jpeg_encode(self._h, _vp(array), cols, rows, pitch, nc, restart_mcus, out, cap, n),
+                               rows * cols * nc, bound)
+
+    def dev_jpeg_encode(self, d_pixels: int, cols: int, rows: int, pitch_bytes: int, components: int, d_out: int, out_capacity: int,
+                        restart_mcus: int = 0) -> int:
+        """jpeg_encode with the raster and the file in device memory -> the file's length.  A file that does not fit raises
+        SarproHipError with code ERR_BUFFER_TOO_SMALL and the size it needs in `.needed`; nothing past the capacity is written."""
+        n = C.c_size_t(0)
+        rc = lib.sarpro_hip_jpeg_encode_dev(self._h, _vp(d_pixels), cols, rows, pitch_bytes, components, restart_mcus, _vp(d_out) if d_out else None,
+                                            out_capacity, C.byref(n))
+        if rc == _lib.ERR_BUFFER_TOO_SMALL:
+            e = SarproHipError(rc, (lib.sarpro_hip_last_error(self._h) or b"").decode())
+            e.needed = n.value
+            raise e
+        self._chk(rc)
+        return n.value
+
+    def dualpol_synrgb_resized_jpeg(self, band1: np.ndarray, band2: np.ndarray, strategy: AutoscaleStrategy, target_size: int | None, pad: bool,
+                                    mode: SyntheticRgbMode = SyntheticRgbMode.Default, restart_mcus: int = 0):
+        """dualpol_synrgb_resized up to the file the reference writes -> (JPEG bytes, ResizeMeta); the RGB raster stays on the device."""
+        from ._lib import ResizeMeta
+        rows, cols = band1.shape
+        fc, fr = resize_output_dims(cols, rows, target_size, pad)
+        m = ResizeMeta()
+        b1 = np.ascontiguousarray(band1, np.uint16)
+        b2 = np.ascontiguousarray(band2, np.uint16)
+        data = self._jpeg_call(lambda out, cap, n: lib.sarpro_hip_dualpol_synrgb_resized_u16_jpeg(
+            self._h, _vp(b1), _vp(b2), rows, cols, int(strategy), int(mode), target_size or 0, int(pad), out, cap, n, restart_mcus, C.byref(m)),
+            fr * fc * 3, jpeg_bound(fc, fr, 3, restart_mcus))
+        return data, m
+
+    def dualpol_synrgb_resized_f32_jpeg(self, band1: np.ndarray, band2: np.ndarray, strategy: AutoscaleStrategy, target_size: int | None, pad: bool,
+                                        mode: SyntheticRgbMode = SyntheticRgbMode.Default, plain_pipeline: bool = False, restart_mcus: int = 0):
+        """dualpol_synrgb_resized_f32 up to the file -> (JPEG bytes, ResizeMeta)."""
+        from ._lib import ResizeMeta
+        rows, cols = band1.shape
+        fc, fr = resize_output_dims(cols, rows, target_size, pad)
+        m = ResizeMeta()
+        b1 = np.ascontiguousarray(band1, np.float32)
+        b2 = np.ascontiguousarray(band2, np.float32)
+        data = self._jpeg_call(lambda out, cap, n: lib.sarpro_hip_dualpol_synrgb_resized_f32_jpeg(
+            self._h, _vp(b1), _vp(b2), rows, cols, int(strategy), int(mode), 1 if plain_pipeline else 0, target_size or 0, int(pad), out, cap, n,
+            restart_mcus, C.byref(m)), fr * fc * 3, jpeg_bound(fc, fr, 3, restart_mcus))
+        return data, m
+
     def save_processed_image_raster(self, processed: np.ndarray, bit_depth: BitDepth, strategy: AutoscaleStrategy,
                                     target_size: int | None, pad: bool):
         """save_processed_image (save.rs:23-170) up to the raster its writer receives -> (raster, ResizeMeta)."""
@@ -844,6 +914,25 @@ def resize_output_dims(cols: int, rows: int, target_size: int | None, pad: bool)
     if rc:
         raise SarproHipError(rc, "resize_output_dims")
     return fc.value, fr.value
+
+
+def host_jpeg_header(cols: int, rows: int, components: int, restart_mcus: int = 0) -> bytes:
+    """The JPEG file of the encoder up to and including its SOS header (no GPU)."""
+    buf = np.empty(1024, np.uint8)
+    n = C.c_size_t(0)
+    rc = lib.sarpro_hip_host_jpeg_header(cols, rows, components, restart_mcus, _vp(buf), buf.size, C.byref(n))
+    if rc != _lib.OK:
+        raise SarproHipError(rc, "host_jpeg_header: cols and rows 1..65535, components 1 or 3, restart interval 0..65535")
+    return buf[:n.value].tobytes()
+
+
+def jpeg_bound(cols: int, rows: int, components: int, restart_mcus: int = 0) -> int:
+    """A capacity no JPEG file of this shape can exceed (no GPU)."""
+    n = C.c_size_t(0)
+    rc = lib.sarpro_hip_jpeg_bound(cols, rows, components, restart_mcus, C.byref(n))
+    if rc != _lib.OK:
+        raise SarproHipError(rc, "jpeg_bound: cols and rows 1..65535, components 1 or 3, restart interval 0..65535")
+    return n.value
 
 
 def batch_dualpol_synrgb_resized(devices, scenes, strategy, target_size, pad, mode=SyntheticRgbMode.Default,
