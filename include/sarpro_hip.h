@@ -476,6 +476,71 @@ int sarpro_hip_dualpol_synrgb_resized_stream_u16(sarpro_hip_ctx *ctx, sarpro_hip
                                                  size_t cols, int strategy, int mode, size_t target_size, int pad, uint8_t *rgb_out,
                                                  sarpro_hip_resize_meta *meta);
 
+/* ================= downsample on read (io/sentinel1.rs:1074-1108 -> io/gdal.rs:145-177) =================
+ * The reference's default flow does not process full-resolution bands: SafeReader::open_with_options(.., target_size) has GDAL
+ * resample each band while reading it (read_band_resampled), the long side going to target_size, and the raster core sees the
+ * resulting few-MP non-integer f32 bands.  The filter is ResampleAlg::Average when the reduction is >= 4 (every GRD quicklook) and
+ * Lanczos below (sentinel1.rs:1093-1102).  This section is that step for u16 bands and the Average filter, on the device.
+ *   shape   scale = min(ts / max(cols, rows), 1) in f64; out = max(round(n * scale), 1) per axis, round half away from zero.
+ *   filter  the separable weighted box: per axis, destination sample j of m covers [j * r, min((j + 1) * r, n)) with r = n / m;
+ *           a source sample weighs its overlap with that interval (1 for every interior sample).  Per destination pixel, for each
+ *           source row of the window top to bottom: the EXACT integer sum of the interior columns plus the two edge samples times
+ *           their weights (f64), times the row's weight, added to the running f64 sum; one correctly rounded division by
+ *           w_sum_x * w_sum_y; one rounding to f32.  DESIGN.md 9b states it operation by operation; tests/readref.py is its
+ *           restatement.  The results are a function of the definition alone (bit for bit, whatever the tiling or pitch).
+ * Parity with GDAL's own Average is UNPINNED: GDAL is absent here and the reference does not lock its version; this is the weighted
+ * box GDAL's average resampler documents, in its working precision for a Float32 buffer.  Lanczos on read (GDAL's kernel, reductions
+ * below 4) is not built: such a request returns SARPRO_HIP_ERR_UNSUPPORTED. */
+#define SARPRO_HIP_ERR_UNSUPPORTED (-10) /* a documented combination that is not built (Lanczos on read) */
+typedef enum {
+    SARPRO_READ_DEFAULT = -1, /* the rule of sentinel1.rs:1093-1102 */
+    SARPRO_READ_AVERAGE = 0,
+    SARPRO_READ_LANCZOS = 1
+} sarpro_hip_read_alg;
+/* sentinel1.rs:1084-1102 (no GPU): the shape a band of cols x rows is read at, and the filter the rule picks for it (*alg =
+ * SARPRO_READ_AVERAGE iff max(cols, rows) / target_size >= 4).  cols, rows or target_size = 0, a null pointer: INVALID_ARG. */
+int sarpro_hip_read_output_dims(size_t cols, size_t rows, size_t target_size, size_t *out_cols, size_t *out_rows, int *alg);
+/* One axis of the Average filter (no GPU): for each of the n_dst destination samples its window [first, first + count) of the n_src
+ * source samples, the weights of the window's first and last sample (a one-sample window: w_first alone, w_last = 0) and the window's
+ * total weight.  1 <= n_dst <= n_src <= 2^30; arrays of n_dst entries. */
+int sarpro_hip_host_read_average_axis(size_t n_src, size_t n_dst, uint32_t first[], uint32_t count[], double w_first[], double w_last[],
+                                      double w_sum[]);
+/* The Average filter: rows x cols u16 (in_pitch elements per row) -> out_rows x out_cols f32 (out_pitch elements per row), both in
+ * device memory; 1 <= out_rows <= rows, 1 <= out_cols <= cols (a ratio of 1 is the plain u16 -> f32 cast).  Stream-ordered on the
+ * context's stream and synchronous like the other _dev calls (on a SARPRO_HIP_CTX_ASYNC_DEV context it returns once enqueued).
+ * 16-byte loads when in_pitch % 8 == 0 and d_in is 16-byte aligned (the raster is rows x in_pitch elements, as everywhere in this
+ * header: the last vector of a row may reach into the row's padding, whose values are never used), element loads otherwise: the same
+ * results.  Kernel time: read_average. */
+int sarpro_hip_read_average_u16_dev(sarpro_hip_ctx *ctx, const uint16_t *d_in, size_t rows, size_t cols, size_t in_pitch, size_t out_rows,
+                                    size_t out_cols, float *d_out_f32, size_t out_pitch);
+/* The same with host pointers (compact rasters): the band goes up, the averaged raster comes back. */
+int sarpro_hip_read_average_u16(sarpro_hip_ctx *ctx, const uint16_t *in, size_t rows, size_t cols, size_t out_rows, size_t out_cols,
+                                float *out_f32);
+/* "Two measurement bands in, quicklook RGB out, as --size N does it": the shape of sarpro_hip_read_output_dims, both bands averaged
+ * (one launch) into f32 rasters of the context, then sarpro_hip_dualpol_synrgb_resized_f32_dev on them with the caller's flags
+ * (SARPRO_HIP_DUALPOL_PLAIN_PIPELINE or 0).  The bands arrive at target_size already, so the resize step takes its early-out and
+ * only the pad remains, as in the reference.  d_rgb_out: final_rows * final_cols * 3 bytes, where (final_cols, final_rows) =
+ * sarpro_hip_resize_output_dims(out_cols, out_rows, target_size, pad).  alg: SARPRO_READ_DEFAULT follows the rule; an explicit
+ * SARPRO_READ_AVERAGE is honoured at any reduction >= 1; Lanczos, chosen by the rule or requested, returns
+ * SARPRO_HIP_ERR_UNSUPPORTED with a message naming the reduction (nothing is written). */
+int sarpro_hip_dualpol_synrgb_read_u16_dev(sarpro_hip_ctx *ctx, const uint16_t *d_band1, const uint16_t *d_band2, size_t rows, size_t cols,
+                                           size_t in_pitch, int alg, int strategy, int mode, unsigned flags, size_t target_size, int pad,
+                                           uint8_t *d_rgb_out, sarpro_hip_resize_meta *meta);
+/* Host u16 bands in (compact), host RGB out: only the raw DNs and the product cross PCIe. */
+int sarpro_hip_dualpol_synrgb_read_u16(sarpro_hip_ctx *ctx, const uint16_t *band1, const uint16_t *band2, size_t rows, size_t cols, int alg,
+                                       int strategy, int mode, unsigned flags, size_t target_size, int pad, uint8_t *rgb_out,
+                                       sarpro_hip_resize_meta *meta);
+/* The bands through a row reader and the pinned ring (as sarpro_hip_dualpol_synrgb_resized_stream_u16), then the device steps above. */
+int sarpro_hip_dualpol_synrgb_read_stream_u16(sarpro_hip_ctx *ctx, sarpro_hip_row_reader reader, void *reader_user, size_t rows, size_t cols,
+                                              int alg, int strategy, int mode, unsigned flags, size_t target_size, int pad, uint8_t *rgb_out,
+                                              sarpro_hip_resize_meta *meta);
+/* The same up to the FILE: the RGB raster stays on the device and is encoded there (the contract of the other _jpeg flows: when the
+ * file does not fit, *jpeg_bytes_out is the size it needs and the status is SARPRO_HIP_ERR_BUFFER_TOO_SMALL). */
+int sarpro_hip_dualpol_synrgb_read_stream_u16_jpeg(sarpro_hip_ctx *ctx, sarpro_hip_row_reader reader, void *reader_user, size_t rows,
+                                                   size_t cols, int alg, int strategy, int mode, unsigned flags, size_t target_size, int pad,
+                                                   uint8_t *jpeg_out, size_t jpeg_capacity, size_t *jpeg_bytes_out, unsigned restart_mcus,
+                                                   sarpro_hip_resize_meta *meta);
+
 /* ---- file shims for the two callbacks: uncompressed strip TIFF / BigTIFF (what Sentinel-1 GRD measurement rasters
  * are; io/gdal.rs:107-141 and io/writers/tiff.rs:6-78 go through GDAL).  Baseline TIFF 6.0 + BigTIFF, II or MM,
  * Compression = 1, strips, 8- / 16-bit unsigned samples, chunky or planar; anything else fails with

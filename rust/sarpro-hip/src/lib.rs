@@ -415,6 +415,53 @@ impl RasterCore {
             rgb: Some(rgb), gray_band2: None, gray16_band2: None, resize: meta })
     }
 
+    // ------------------------------------------------------------------ downsample on read (io/sentinel1.rs:1074-1108, io/gdal.rs:145-177)
+    /// sentinel1.rs:1084-1102: the shape a band is read at for `target_size` and whether the rule picks `ResampleAlg::Average`
+    /// (reduction >= 4) -> (out_cols, out_rows, average).
+    pub fn read_output_dims(cols: usize, rows: usize, target_size: usize) -> Result<(usize, usize, bool)> {
+        let (mut oc, mut orows, mut alg) = (0usize, 0usize, 0 as c_int);
+        let rc = unsafe { sys::sarpro_hip_read_output_dims(cols, rows, target_size, &mut oc, &mut orows, &mut alg) };
+        if rc != sys::SARPRO_HIP_OK {
+            return Err(HipError { code: rc, message: "read_output_dims: cols, rows and target_size must be positive".into() });
+        }
+        Ok((oc, orows, alg == sys::SARPRO_READ_AVERAGE))
+    }
+
+    /// `GdalSarReader::read_band_resampled(1, out_cols, out_rows, Some(ResampleAlg::Average))` (io/gdal.rs:145-177) for a u16
+    /// measurement band held in memory: the area average on the device.  Parity with GDAL's own filter is unpinned.
+    pub fn try_read_band_resampled(&self, band: &Array2<u16>, out_cols: usize, out_rows: usize) -> Result<Array2<f32>> {
+        let (rows, cols) = band.dim();
+        let b = band.as_standard_layout();
+        let mut out = vec![0f32; out_cols * out_rows];
+        self.chk(unsafe { sys::sarpro_hip_read_average_u16(self.ctx, b.as_ptr(), rows, cols, out_rows, out_cols, out.as_mut_ptr()) })?;
+        Array2::from_shape_vec((out_rows, out_cols), out)
+            .map_err(|_| HipError { code: sys::SARPRO_HIP_ERR_SHAPE_MISMATCH, message: "output shape".into() })
+    }
+
+    /// The default flow from the raw bands (sentinel1.rs:1103-1105 per band, then api/mod.rs:404-437 when `plain_pipeline`, save.rs:317-367
+    /// otherwise): both u16 bands averaged on read to the long side `target_size`, per-band u8, pad, synRGB.  `average = None` follows
+    /// the reference's rule (Lanczos below a reduction of 4 is not built: `SARPRO_HIP_ERR_UNSUPPORTED`), `Some(true)` averages at
+    /// any reduction.
+    pub fn try_render_multiband_image_read_u16(&self, band1: &Array2<u16>, band2: &Array2<u16>, target_size: usize, pad: bool,
+        autoscale: AutoscaleStrategy, syn_mode: SyntheticRgbMode, plain_pipeline: bool, average: Option<bool>) -> Result<ProcessedImage> {
+        if band1.dim() != band2.dim() {
+            return Err(HipError { code: sys::SARPRO_HIP_ERR_SHAPE_MISMATCH, message: "band shapes differ".into() });
+        }
+        let (rows, cols) = band1.dim();
+        let (b1, b2) = (band1.as_standard_layout(), band2.as_standard_layout());
+        let (oc, orows, _) = Self::read_output_dims(cols, rows, target_size)?;
+        let (mut fc, mut fr) = (0usize, 0usize);
+        self.chk(unsafe { sys::sarpro_hip_resize_output_dims(oc, orows, target_size, pad as c_int, &mut fc, &mut fr) })?;
+        let alg = match average { None => sys::SARPRO_READ_DEFAULT, Some(true) => sys::SARPRO_READ_AVERAGE, Some(false) => sys::SARPRO_READ_LANCZOS };
+        let flags = if plain_pipeline { sys::SARPRO_HIP_DUALPOL_PLAIN_PIPELINE } else { 0 };
+        let mut rgb = vec![0u8; fc * fr * 3];
+        let mut meta = zeroed_meta();
+        self.chk(unsafe { sys::sarpro_hip_dualpol_synrgb_read_u16(self.ctx, b1.as_ptr(), b2.as_ptr(), rows, cols, alg, autoscale as c_int,
+            syn_mode as c_int, flags, target_size, pad as c_int, rgb.as_mut_ptr(), &mut meta) })?;
+        Ok(ProcessedImage { width: fc, height: fr, bit_depth: BitDepth::U8, format: OutputFormat::JPEG, gray: None, gray16: None,
+            rgb: Some(rgb), gray_band2: None, gray16_band2: None, resize: meta })
+    }
+
     // ------------------------------------------------------------------ device-pointer entry points (rasters resident in HBM)
     /// `d_*` are device addresses; pitches in elements.  See include/sarpro_hip.h for the stream-ordering contract.
     pub unsafe fn dev_dualpol_synrgb_u16(&self, d_band1: *const u16, d_band2: *const u16, rows: usize, cols: usize, in_pitch: usize,

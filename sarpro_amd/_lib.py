@@ -16,6 +16,8 @@ OK = 0
 ERR_INVALID_ARG, ERR_SHAPE_MISMATCH, ERR_UNSUPPORTED_SHAPE = -1, -2, -3
 ERR_HIP, ERR_RCCL, ERR_OOM, ERR_NO_DEVICE, ERR_IO = -4, -5, -6, -7, -8
 ERR_BUFFER_TOO_SMALL = -9
+ERR_UNSUPPORTED = -10
+READ_DEFAULT, READ_AVERAGE, READ_LANCZOS = -1, 0, 1  # sarpro_hip_read_alg
 
 
 class Stats(C.Structure):
@@ -111,6 +113,9 @@ SYMBOLS = [
     "sarpro_hip_local_group_create", "sarpro_hip_local_group_destroy", "sarpro_hip_comm_init_local", "sarpro_hip_host_clahe_saturated_levels", "sarpro_hip_ctx_set_attr", "sarpro_hip_ctx_reset_attr", "sarpro_hip_ctx_get_attr", "sarpro_hip_attr_name",
     "sarpro_hip_host_jpeg_header", "sarpro_hip_jpeg_bound", "sarpro_hip_jpeg_encode_dev", "sarpro_hip_jpeg_encode",
     "sarpro_hip_dualpol_synrgb_resized_u16_jpeg", "sarpro_hip_dualpol_synrgb_resized_f32_jpeg",
+    "sarpro_hip_read_output_dims", "sarpro_hip_host_read_average_axis", "sarpro_hip_read_average_u16_dev", "sarpro_hip_read_average_u16",
+    "sarpro_hip_dualpol_synrgb_read_u16_dev", "sarpro_hip_dualpol_synrgb_read_u16", "sarpro_hip_dualpol_synrgb_read_stream_u16",
+    "sarpro_hip_dualpol_synrgb_read_stream_u16_jpeg",
 ]
 
 if not os.path.exists(LIB_PATH):
@@ -282,3 +287,11 @@ _proto("sarpro_hip_jpeg_encode_dev", _i, _vp, _vp, _sz, _sz, _sz, _i, _u, _vp, _
 _proto("sarpro_hip_jpeg_encode", _i, _vp, _vp, _sz, _sz, _sz, _i, _u, _vp, _sz, C.POINTER(_sz))
 _proto("sarpro_hip_dualpol_synrgb_resized_u16_jpeg", _i, _vp, _vp, _vp, _sz, _sz, _i, _i, _sz, _i, _vp, _sz, C.POINTER(_sz), _u, _M)
 _proto("sarpro_hip_dualpol_synrgb_resized_f32_jpeg", _i, _vp, _vp, _vp, _sz, _sz, _i, _i, _u, _sz, _i, _vp, _sz, C.POINTER(_sz), _u, _M)
+_proto("sarpro_hip_read_output_dims", _i, _sz, _sz, _sz, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_i))
+_proto("sarpro_hip_host_read_average_axis", _i, _sz, _sz, _vp, _vp, _vp, _vp, _vp)
+_proto("sarpro_hip_read_average_u16_dev", _i, _vp, _vp, _sz, _sz, _sz, _sz, _sz, _vp, _sz)
+_proto("sarpro_hip_read_average_u16", _i, _vp, _vp, _sz, _sz, _sz, _sz, _vp)
+_proto("sarpro_hip_dualpol_synrgb_read_u16_dev", _i, _vp, _vp, _vp, _sz, _sz, _sz, _i, _i, _i, _u, _sz, _i, _vp, _M)
+_proto("sarpro_hip_dualpol_synrgb_read_u16", _i, _vp, _vp, _vp, _sz, _sz, _i, _i, _i, _u, _sz, _i, _vp, _M)
+_proto("sarpro_hip_dualpol_synrgb_read_stream_u16", _i, _vp, _vp, _vp, _sz, _sz, _i, _i, _i, _u, _sz, _i, _vp, _M)
+_proto("sarpro_hip_dualpol_synrgb_read_stream_u16_jpeg", _i, _vp, _vp, _vp, _sz, _sz, _i, _i, _i, _u, _sz, _i, _vp, _sz, C.POINTER(_sz), _u, _M)

@@ -432,6 +432,80 @@ class Context:
             restart_mcus, C.byref(m)), fr * fc * 3, jpeg_bound(fc, fr, 3, restart_mcus))
         return data, m
 
+    # ------------------------------------------------------------------ io/sentinel1.rs:1074-1108 -> io/gdal.rs:145-177
+    def read_average(self, band: np.ndarray, out_rows: int, out_cols: int) -> np.ndarray:
+        """read_band_resampled with ResampleAlg::Average for a u16 band: (rows, cols) uint16 -> (out_rows, out_cols) float32."""
+        b = np.ascontiguousarray(band, np.uint16)
+        rows, cols = b.shape
+        out = np.empty((out_rows, out_cols), np.float32)
+        self._chk(lib.sarpro_hip_read_average_u16(self._h, _vp(b), rows, cols, out_rows, out_cols, _vp(out)))
+        return out
+
+    def dev_read_average(self, d_in: int, rows: int, cols: int, in_pitch: int, out_rows: int, out_cols: int, d_out: int, out_pitch: int):
+        """read_average with the u16 band (in_pitch elements per row) and the f32 raster (out_pitch elements per row) in device memory."""
+        self._chk(lib.sarpro_hip_read_average_u16_dev(self._h, _vp(d_in), rows, cols, in_pitch, out_rows, out_cols, _vp(d_out), out_pitch))
+
+    @staticmethod
+    def _read_final_dims(cols: int, rows: int, target_size: int, pad: bool):
+        oc, orows, _ = read_output_dims(cols, rows, target_size)
+        return resize_output_dims(oc, orows, target_size, pad)
+
+    def dualpol_synrgb_read(self, band1: np.ndarray, band2: np.ndarray, strategy: AutoscaleStrategy, target_size: int, pad: bool,
+                            mode: SyntheticRgbMode = SyntheticRgbMode.Default, plain_pipeline: bool = False, alg: int = _lib.READ_DEFAULT):
+        """Two full-resolution u16 bands -> the quicklook RGB as `--size N` makes it: both bands averaged on read to the long side
+        `target_size`, then dualpol_synrgb_resized_f32 on the f32 bands -> ((final_rows, final_cols, 3) RGB, ResizeMeta)."""
+        from ._lib import ResizeMeta
+        rows, cols = band1.shape
+        fc, fr = self._read_final_dims(cols, rows, target_size, pad)
+        rgb = np.empty((fr, fc, 3), np.uint8)
+        m = ResizeMeta()
+        b1 = np.ascontiguousarray(band1, np.uint16)
+        b2 = np.ascontiguousarray(band2, np.uint16)
+        self._chk(lib.sarpro_hip_dualpol_synrgb_read_u16(self._h, _vp(b1), _vp(b2), rows, cols, int(alg), int(strategy), int(mode),
+                                                         1 if plain_pipeline else 0, target_size, int(pad), _vp(rgb), C.byref(m)))
+        return rgb, m
+
+    def dev_dualpol_synrgb_read(self, d_b1: int, d_b2: int, rows: int, cols: int, in_pitch: int, strategy: AutoscaleStrategy, target_size: int,
+                                pad: bool, d_rgb: int, mode: SyntheticRgbMode = SyntheticRgbMode.Default, plain_pipeline: bool = False,
+                                alg: int = _lib.READ_DEFAULT):
+        """dualpol_synrgb_read with the bands and the compact final_rows x final_cols x 3 RGB raster in device memory."""
+        from ._lib import ResizeMeta
+        m = ResizeMeta()
+        self._chk(lib.sarpro_hip_dualpol_synrgb_read_u16_dev(self._h, _vp(d_b1), _vp(d_b2), rows, cols, in_pitch, int(alg), int(strategy), int(mode),
+                                                             1 if plain_pipeline else 0, target_size, int(pad), _vp(d_rgb), C.byref(m)))
+        return m
+
+    def dualpol_synrgb_read_stream(self, reader, rows: int, cols: int, strategy, target_size: int, pad: bool, mode=SyntheticRgbMode.Default,
+                                   plain_pipeline: bool = False, alg: int = _lib.READ_DEFAULT):
+        """dualpol_synrgb_read with the bands coming through a row reader (see dualpol_synrgb_stream) -> (RGB, ResizeMeta)."""
+        fc, fr = self._read_final_dims(cols, rows, target_size, pad)
+        rgb = np.empty((fr, fc, 3), np.uint8)
+        m = _lib.ResizeMeta()
+        rf, ru, _keep = self._as_reader(reader, cols)
+        self._chk(lib.sarpro_hip_dualpol_synrgb_read_stream_u16(self._h, rf, ru, rows, cols, int(alg), int(strategy), int(mode),
+                                                                1 if plain_pipeline else 0, target_size, int(pad), _vp(rgb), C.byref(m)))
+        return rgb, m
+
+    def dualpol_synrgb_read_stream_jpeg(self, reader, rows: int, cols: int, strategy, target_size: int, pad: bool, mode=SyntheticRgbMode.Default,
+                                        plain_pipeline: bool = False, alg: int = _lib.READ_DEFAULT, restart_mcus: int = 0, capacity: int | None = None):
+        """The same up to the file -> (JPEG bytes, ResizeMeta).  The bands are read once per attempt: the first buffer is the
+        encoder's bound (no file exceeds it) unless `capacity` offers less, in which case a file that does not fit raises
+        SarproHipError with code ERR_BUFFER_TOO_SMALL and the size it needs in `.needed`."""
+        fc, fr = self._read_final_dims(cols, rows, target_size, pad)
+        cap = jpeg_bound(fc, fr, 3, restart_mcus) if capacity is None else capacity
+        buf = np.empty(max(cap, 1), np.uint8)
+        n = C.c_size_t(0)
+        m = _lib.ResizeMeta()
+        rf, ru, _keep = self._as_reader(reader, cols)
+        rc = lib.sarpro_hip_dualpol_synrgb_read_stream_u16_jpeg(self._h, rf, ru, rows, cols, int(alg), int(strategy), int(mode), 1 if plain_pipeline else 0,
+                                                                target_size, int(pad), _vp(buf), cap, C.byref(n), restart_mcus, C.byref(m))
+        if rc == _lib.ERR_BUFFER_TOO_SMALL:
+            e = SarproHipError(rc, (lib.sarpro_hip_last_error(self._h) or b"").decode())
+            e.needed = n.value
+            raise e
+        self._chk(rc)
+        return buf[:n.value].tobytes(), m
+
     def save_processed_image_raster(self, processed: np.ndarray, bit_depth: BitDepth, strategy: AutoscaleStrategy,
                                     target_size: int | None, pad: bool):
         """save_processed_image (save.rs:23-170) up to the raster its writer receives -> (raster, ResizeMeta)."""
@@ -933,6 +1007,27 @@ def jpeg_bound(cols: int, rows: int, components: int, restart_mcus: int = 0) -> 
     if rc != _lib.OK:
         raise SarproHipError(rc, "jpeg_bound: cols and rows 1..65535, components 1 or 3, restart interval 0..65535")
     return n.value
+
+
+def read_output_dims(cols: int, rows: int, target_size: int):
+    """sentinel1.rs:1084-1102 (no GPU): the shape a cols x rows band is read at for `target_size`, and the filter the rule picks
+    -> (out_cols, out_rows, READ_AVERAGE | READ_LANCZOS)."""
+    oc, orows, alg = C.c_size_t(0), C.c_size_t(0), C.c_int(0)
+    rc = lib.sarpro_hip_read_output_dims(cols, rows, target_size, C.byref(oc), C.byref(orows), C.byref(alg))
+    if rc != _lib.OK:
+        raise SarproHipError(rc, "read_output_dims: cols, rows and target_size must be positive")
+    return oc.value, orows.value, alg.value
+
+
+def host_read_average_axis(n_src: int, n_dst: int):
+    """One axis of the Average filter (no GPU) -> (first, count, w_first, w_last, w_sum): uint32, uint32, f64, f64, f64 arrays."""
+    n = max(int(n_dst), 0)
+    first, count = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+    wf, wl, ws = np.zeros(n, np.float64), np.zeros(n, np.float64), np.zeros(n, np.float64)
+    rc = lib.sarpro_hip_host_read_average_axis(n_src, n_dst, _vp(first), _vp(count), _vp(wf), _vp(wl), _vp(ws))
+    if rc != _lib.OK:
+        raise SarproHipError(rc, "host_read_average_axis: 1 <= n_dst <= n_src <= 2^30")
+    return first, count, wf, wl, ws
 
 
 def batch_dualpol_synrgb_resized(devices, scenes, strategy, target_size, pad, mode=SyntheticRgbMode.Default,

@@ -230,6 +230,11 @@ struct sarpro_hip_ctx {
     // their RGB raster and the file before it crosses PCIe; pinned: the scan's length (8 bytes) and the header
     sarpro::DevBuf jpeg_coef, jpeg_seg, jpeg_tables, jpeg_band[2], jpeg_rgb, jpeg_file;
     sarpro::PinnedBuf jpeg_host;
+    // downsample on read (read_path.cpp): the two axes' window tables (device, and the pinned stage they are built in) with the shape
+    // they were built for (rows, cols, out_rows, out_cols); the flows' staged u16 bands and their averaged f32 rasters
+    sarpro::DevBuf read_tab, read_src[2], read_band[2];
+    sarpro::PinnedBuf read_host;
+    size_t read_key[4] = {0, 0, 0, 0};
     sarpro::DevBuf chain_consts;                 // device-resident chain: dB table | suppressed lut_r/g per floor | blue pairs
     sarpro::DevBuf chain_scratch;               // statistics step: per-slice partials | 4096 bins per band
     sarpro::DevBuf chain_state;                  // ChainBandState[2] | resc[2][256] | identity[2] | floor

@@ -59,6 +59,10 @@ int band_u8_table_dev(sarpro_hip_ctx *ctx, const uint16_t *d_in, size_t rows, si
 // both bands of a dual-pol product in one chain (nb = 2; Tamed: band 0 copol, band 1 crosspol) or one band (nb = 1, as above); out[nb]
 int bands_u8_table_dev(sarpro_hip_ctx *ctx, const uint16_t *const d_in[], int nb, size_t rows, size_t cols, size_t in_pitch, int strategy, int tamed,
                        ResizeLutSrc *out);
+// the JPEG file of a raster in device memory into a host buffer (jpeg_path.cpp; the contract of sarpro_hip_jpeg_encode: BUFFER_TOO_SMALL
+// with the needed size in *bytes_out); restart_mcus = 0: the library's interval
+int jpeg_encode_to_host(sarpro_hip_ctx *ctx, const uint8_t *d_pixels, size_t cols, size_t rows, size_t pitch_bytes, int components, unsigned restart_mcus,
+                        uint8_t *out, size_t out_capacity, size_t *bytes_out);
 int comm_allreduce_sum_u64_async(sarpro_hip_ctx *ctx, uint64_t *d_buf, size_t count);
 void comm_replay_rewind(sarpro_hip_ctx *ctx);   // start of a stripe call: COMM_REPLAY answers from the first recorded buffer again (COMM_RECORD: forget the old ones)
 void comm_saved_release(sarpro_hip_ctx *ctx);

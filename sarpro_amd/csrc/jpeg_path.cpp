@@ -219,6 +219,14 @@ int encode_to_host(sarpro_hip_ctx *ctx, const uint8_t *d_pixels, size_t cols, si
 
 } // namespace
 
+namespace sarpro {
+int jpeg_encode_to_host(sarpro_hip_ctx *ctx, const uint8_t *d_pixels, size_t cols, size_t rows, size_t pitch_bytes, int components, unsigned restart_mcus,
+                        uint8_t *out, size_t out_capacity, size_t *bytes_out) {
+    if (!args_ok(cols, rows, components, restart_mcus)) return fail(ctx, SARPRO_HIP_ERR_INVALID_ARG, "jpeg: cols and rows 1..65535, components 1 or 3, restart interval 0..65535");
+    return encode_to_host(ctx, d_pixels, cols, rows, pitch_bytes, components, restart_mcus ? restart_mcus : kJpegDefaultRestartMcus, out, out_capacity, bytes_out);
+}
+} // namespace sarpro
+
 extern "C" int sarpro_hip_host_jpeg_header(size_t cols, size_t rows, int components, unsigned restart_mcus, uint8_t *out, size_t cap, size_t *bytes) {
     if (!args_ok(cols, rows, components, restart_mcus) || !bytes || (!out && cap)) return SARPRO_HIP_ERR_INVALID_ARG;
     const unsigned R = restart_mcus ? restart_mcus : kJpegDefaultRestartMcus;

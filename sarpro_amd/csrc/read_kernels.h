@@ -1,0 +1,40 @@
+// read_kernels.h -- launch interface of the downsample-on-read pass (read_kernels.hip): the area average of u16 bands to f32 that
+// SafeReader::open_with_options(.., target_size) asks of GDAL (io/sentinel1.rs:1074-1108 -> io/gdal.rs:145-177, ResampleAlg::Average).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+namespace sarpro {
+
+// One destination sample of one axis: its window [first, first + count) of source samples and the weights of the window's two edge
+// samples (interior samples weigh exactly 1; a one-sample window has the single weight w_first and w_last = 0).  Built on the host
+// (read_path.cpp: read_average_axis), 32 bytes.
+struct ReadAxis {
+    uint32_t first, count;
+    double w_first, w_last, w_sum;
+};
+
+constexpr uint32_t kReadThreads = 256;    // one lane per destination column of a strip
+constexpr uint32_t kReadChunk = 3072;     // source samples of one row that one LDS slab holds
+constexpr uint32_t kReadUnits = 4;        // slabs per stage (two stages in LDS: 48 KiB)
+constexpr uint32_t kReadMaxBandRows = 32; // destination rows of a workgroup's tile
+
+struct ReadArgs {
+    const uint16_t *src[2]; // nbands rasters of the same shape and pitch
+    float *dst[2];
+    uint32_t nbands;
+    uint32_t rows, cols, out_rows, out_cols;
+    size_t in_pitch, out_pitch; // elements
+    const ReadAxis *col_tab;    // [out_cols], device
+    const ReadAxis *row_tab;    // [out_rows]
+    uint32_t strip_cols;        // destination columns per tile, 1..kReadThreads
+    uint32_t band_rows;         // destination rows per tile, 1..kReadMaxBandRows
+    uint32_t max_span;          // the widest strip's span of source columns, from its first window's vector boundary to its last window's end
+};
+
+// vec: 16-byte loads (in_pitch % 8 == 0 and both bases 16-byte aligned); otherwise element loads with the same results
+hipError_t launch_read_average_u16(const ReadArgs &a, bool vec, hipStream_t s);
+
+} // namespace sarpro

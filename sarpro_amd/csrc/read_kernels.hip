@@ -1,0 +1,179 @@
+// read_kernels.hip -- downsample on read: the area average of u16 bands to f32 (io/sentinel1.rs:1074-1108 -> io/gdal.rs:145-177 with
+// ResampleAlg::Average), DESIGN.md 9b.  A destination pixel is the separable weighted box over its source window: per source row the
+// EXACT integer sum of the window's interior columns plus the two edge samples times their f64 weights, the rows of the window
+// accumulated top to bottom in f64 with the row weights, one correctly rounded division by the window's weight, one rounding to f32.
+// Only the integer sum is order-free, and it is exact: every f64 operation happens in the order of the definition, so the result
+// does not depend on the tiling.  (-ffp-contract=off: no product is fused into a sum.)
+//
+// A workgroup owns a tile: a strip of <= 256 destination columns (one lane each) x a band of <= 32 destination rows.  It walks the
+// source rows of the band top to bottom; every row's span of source columns is cut into slabs of kReadChunk samples (one slab for every
+// reduction up to ~12 at full strips; the host narrows the strip for larger reductions; windows wider than a slab -- a reduction beyond
+// 3072, a single destination sample -- simply take several slabs per row: the lane's sums run across them).  kReadUnits slabs make a
+// stage; two stages live in LDS: while the lanes sum stage s out of LDS, the loads of stage s + 1 are in flight into registers and
+// are written to the other half behind the compiler's counted wait, one barrier per stage.  The row tables of the tile sit in LDS so
+// that no global load inside the loop sits behind the prefetch in the memory counter's order.
+#include "read_kernels.h"
+
+namespace sarpro {
+
+namespace {
+
+constexpr uint32_t kVecPerUnit = kReadChunk / 8;                              // 16-byte vectors of a slab
+constexpr uint32_t kLoadsPerLane = kReadUnits * kVecPerUnit / kReadThreads;   // 6
+static_assert(kReadUnits * kVecPerUnit % kReadThreads == 0, "a stage is a whole number of vectors per lane");
+static_assert((uint64_t)kReadChunk * 65535u < (1ull << 32), "a slab's interior sum fits 32 bits");
+
+// 8 samples from column a (a multiple of 8, a < cols) of a row; samples at and beyond `cols` are never used.  The vector form reads
+// them from the row's padding (a + 8 <= in_pitch, a multiple of 8: rasters are rows x in_pitch elements), with no branch between
+// the loads of a stage; the element form reads them as 0.
+template <bool VEC>
+__device__ __forceinline__ uint4 read_fetch8(const uint16_t *row, uint32_t a, uint32_t cols) {
+    if (VEC) return *reinterpret_cast<const uint4 *>(row + a);
+    uint32_t w[4];
+#pragma unroll
+    for (uint32_t p = 0; p < 4; ++p) {
+        const uint32_t lo = a + 2 * p < cols ? row[a + 2 * p] : 0u;
+        const uint32_t hi = a + 2 * p + 1 < cols ? row[a + 2 * p + 1] : 0u;
+        w[p] = lo | (hi << 16);
+    }
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+} // namespace
+
+// ONE: every strip's span of source columns fits one slab (the host checks the widest): the slab index, the chunk bounds and the
+// lane's range inside the slab are then constants of the tile, and a row's interior sum fits 32 bits.
+template <bool VEC, bool ONE>
+__global__ __launch_bounds__(kReadThreads) void k_read_average_u16(ReadArgs a) {
+    __shared__ uint4 s_slab[2][kReadUnits][kVecPerUnit];
+    __shared__ ReadAxis s_rows[kReadMaxBandRows];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t nstrips = (a.out_cols + a.strip_cols - 1) / a.strip_cols;
+    const uint32_t nrb = (a.out_rows + a.band_rows - 1) / a.band_rows;
+    uint32_t t = blockIdx.x; // strips fastest: neighbouring workgroups read neighbouring spans of the same source rows
+    const uint32_t strip = t % nstrips;
+    t /= nstrips;
+    const uint32_t rb = t % nrb, band = t / nrb;
+    const uint16_t *src = band ? a.src[1] : a.src[0];
+    float *dst = band ? a.dst[1] : a.dst[0];
+    const uint32_t j0 = strip * a.strip_cols, j1 = min(j0 + a.strip_cols, a.out_cols);
+    const uint32_t i0 = rb * a.band_rows, i1 = min(i0 + a.band_rows, a.out_rows);
+    if (tid < i1 - i0) s_rows[tid] = a.row_tab[i0 + tid];
+    // the tile's source rectangle: columns [cs, ce) (cs on a vector boundary), rows [ys, ye)
+    const ReadAxis cfirst = a.col_tab[j0], clast = a.col_tab[j1 - 1], rfirst = a.row_tab[i0], rlast = a.row_tab[i1 - 1];
+    const uint32_t cs = cfirst.first & ~7u, ce = clast.first + clast.count;
+    const uint32_t ys = rfirst.first, ye = rlast.first + rlast.count;
+    const uint32_t nchunks = ONE ? 1u : (ce - cs + kReadChunk - 1) / kReadChunk;
+    const uint32_t nunits = (ye - ys) * nchunks; // unit u = slab (u % nchunks) of source row ys + u / nchunks
+    const uint32_t nstages = (nunits + kReadUnits - 1) / kReadUnits;
+    // the lane's destination column (idle lanes: an empty window beyond every slab)
+    const bool active = tid < j1 - j0;
+    uint32_t c0 = 0x7fffffffu, c1 = 0x7fffffffu;
+    double cwf = 0.0, cwl = 0.0, cws = 1.0;
+    if (active) {
+        const ReadAxis e = a.col_tab[j0 + tid];
+        c0 = e.first; c1 = e.first + e.count;
+        cwf = e.w_first; cwl = e.w_last; cws = e.w_sum;
+    }
+    const bool wide = c1 - c0 > 1;
+    // the lane's vectors of a stage: vector v = tid + q * 256 is vector v % kVecPerUnit of the stage's unit v / kVecPerUnit
+    uint32_t qy[kLoadsPerLane], qk[kLoadsPerLane];
+#pragma unroll
+    for (uint32_t q = 0; q < kLoadsPerLane; ++q) {
+        const uint32_t ul = (tid + q * kReadThreads) / kVecPerUnit;
+        qy[q] = ys + ul / nchunks;
+        qk[q] = ul % nchunks;
+    }
+    const uint32_t step_y = kReadUnits / nchunks, step_k = kReadUnits % nchunks;
+    uint4 regs[kLoadsPerLane];
+    auto load_stage = [&]() {
+#pragma unroll
+        for (uint32_t q = 0; q < kLoadsPerLane; ++q) {
+            const uint32_t iv = (tid + q * kReadThreads) % kVecPerUnit;
+            const uint32_t col = cs + qk[q] * kReadChunk + iv * 8;
+            regs[q] = make_uint4(0u, 0u, 0u, 0u);
+            if (qy[q] < ye && col < ce) regs[q] = read_fetch8<VEC>(src + (size_t)qy[q] * a.in_pitch, col, a.cols);
+            qk[q] += step_k; qy[q] += step_y;
+            if (qk[q] >= nchunks) { qk[q] -= nchunks; ++qy[q]; }
+        }
+    };
+    auto write_stage = [&](uint32_t half) {
+#pragma unroll
+        for (uint32_t q = 0; q < kLoadsPerLane; ++q) {
+            const uint32_t v = tid + q * kReadThreads;
+            s_slab[half][v / kVecPerUnit][v % kVecPerUnit] = regs[q];
+        }
+    };
+    load_stage();
+    write_stage(0);
+    __syncthreads();
+    // running state: the source row y and its slab k (uniform); the destination row i with its window [r0, r1) (uniform); per lane the
+    // row's interior sum and edge samples, and the window's weighted sum T
+    uint32_t y = ys, k = 0, i = i0;
+    ReadAxis re = s_rows[0];
+    uint32_t r0 = re.first, r1 = re.first + re.count;
+    uint64_t isum = 0;
+    uint32_t vf = 0, vl = 0;
+    double T = 0.0;
+    for (uint32_t s = 0; s < nstages; ++s) {
+        const bool more = s + 1 < nstages;
+        if (more) load_stage();
+        const uint32_t nu = min(kReadUnits, nunits - s * kReadUnits);
+        for (uint32_t ul = 0; ul < nu; ++ul) {
+            const uint16_t *slab = reinterpret_cast<const uint16_t *>(&s_slab[s & 1][ul][0]);
+            const uint32_t cb = cs + k * kReadChunk, cend = min(cb + kReadChunk, ce);
+            const uint32_t lo = max(c0 + 1, cb), hi = min(c1 - 1, cend);
+            uint32_t part = 0;
+#ifndef SARPRO_READ_ABLATE_SUM // (timing variant, tools/build_variant.sh: the pass without the lanes' LDS reads -- loads, staging, row logic, stores)
+            uint32_t c = lo; // (blocks of independent LDS reads: a one-sample loop waits out the LDS latency per sample)
+            for (; c + 8 <= hi; c += 8) {
+                const uint16_t *p = slab + (c - cb);
+                part += ((uint32_t)p[0] + p[1]) + ((uint32_t)p[2] + p[3]) + (((uint32_t)p[4] + p[5]) + ((uint32_t)p[6] + p[7]));
+            }
+            if (c + 4 <= hi) {
+                const uint16_t *p = slab + (c - cb);
+                part += ((uint32_t)p[0] + p[1]) + ((uint32_t)p[2] + p[3]);
+                c += 4;
+            }
+            for (; c < hi; ++c) part += slab[c - cb];
+            isum += part;
+            if (c0 >= cb && c0 < cend) vf = slab[c0 - cb];
+            if (c1 - 1 >= cb && c1 - 1 < cend) vl = slab[c1 - 1 - cb];
+#endif
+            if (k + 1 < nchunks) { ++k; continue; }
+            // the row is complete: its weighted line sum, then the destination row(s) it belongs to
+            double L = (double)isum + cwf * (double)vf;
+            if (wide) L = L + cwl * (double)vl;
+            while (i < i1 && y >= r0) {
+                const double wy = y == r0 ? re.w_first : (y == r1 - 1 ? re.w_last : 1.0);
+                T = T + wy * L;
+                if (y != r1 - 1) break;
+                if (active) dst[(size_t)i * a.out_pitch + j0 + tid] = (float)(T / (cws * re.w_sum));
+                T = 0.0;
+                if (++i < i1) { re = s_rows[i - i0]; r0 = re.first; r1 = re.first + re.count; } // (a fractional boundary: this row opens the next window too)
+            }
+            isum = 0;
+            k = 0; ++y;
+        }
+        if (more) write_stage((s + 1) & 1);
+        __syncthreads();
+    }
+}
+
+hipError_t launch_read_average_u16(const ReadArgs &a, bool vec, hipStream_t s) {
+    const uint64_t nstrips = (a.out_cols + a.strip_cols - 1) / a.strip_cols, nrb = (a.out_rows + a.band_rows - 1) / a.band_rows;
+    const uint64_t grid = nstrips * nrb * a.nbands;
+    if (!grid || grid > 0x7fffffffull || !a.strip_cols || a.strip_cols > kReadThreads || !a.band_rows || a.band_rows > kReadMaxBandRows) return hipErrorInvalidValue;
+#ifdef SARPRO_READ_ABLATE_GENERIC // (timing variant: the several-slabs form at every shape)
+    const bool one = false;
+#else
+    const bool one = a.max_span <= kReadChunk;
+#endif
+    if (vec && one) hipLaunchKernelGGL((k_read_average_u16<true, true>), dim3((unsigned)grid), dim3(kReadThreads), 0, s, a);
+    else if (vec) hipLaunchKernelGGL((k_read_average_u16<true, false>), dim3((unsigned)grid), dim3(kReadThreads), 0, s, a);
+    else if (one) hipLaunchKernelGGL((k_read_average_u16<false, true>), dim3((unsigned)grid), dim3(kReadThreads), 0, s, a);
+    else hipLaunchKernelGGL((k_read_average_u16<false, false>), dim3((unsigned)grid), dim3(kReadThreads), 0, s, a);
+    return hipGetLastError();
+}
+
+} // namespace sarpro

@@ -1,0 +1,279 @@
+// read_path.cpp -- downsample on read (io/sentinel1.rs:1074-1108 -> io/gdal.rs:145-177): SafeReader::open_with_options(.., target_size)
+// has GDAL resample each band while reading it, the long side going to target_size, with ResampleAlg::Average when the reduction is
+// >= 4 (every GRD quicklook) and Lanczos below; the few-MP f32 bands that result are what the raster core processes.  Here: the
+// output shape and the filter rule, the Average filter's per-axis window tables (host, f64, every operation in the order DESIGN.md
+// 9b fixes), the device pass over u16 bands (read_kernels.hip) and the flows "two u16 bands in, quicklook RGB / JPEG out".
+// Parity with GDAL's own Average is unpinned (GDAL is absent, the reference does not lock its version): the definition is the
+// weighted box its average resampler documents, restated in tests/readref.py.  Lanczos on read is not built.
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "api_common.h"
+#include "internal.h"
+#include "read_kernels.h"
+
+using namespace sarpro;
+
+namespace {
+
+constexpr size_t kReadMaxDim = (size_t)1 << 30;
+
+// sentinel1.rs:1084-1102.  f64::round is half away from zero: std::round.
+void read_dims(size_t cols, size_t rows, size_t ts, size_t *oc, size_t *orows, int *alg) {
+    const size_t long_side = std::max(cols, rows);
+    const double scale = std::min((double)ts / (double)long_side, 1.0);
+    *oc = (size_t)std::max(std::round((double)cols * scale), 1.0);
+    *orows = (size_t)std::max(std::round((double)rows * scale), 1.0);
+    const double reduction = std::max((double)long_side / (double)ts, 1.0);
+    *alg = reduction >= 4.0 ? SARPRO_READ_AVERAGE : SARPRO_READ_LANCZOS;
+}
+
+// One axis: destination sample j covers [j * r, min((j + 1) * r, n)), r = n / m.  Plain f64 + - * / in exactly this order.
+void read_average_axis(size_t n, size_t m, ReadAxis *out) {
+    const double r = (double)n / (double)m, nd = (double)n;
+    for (size_t j = 0; j < m; ++j) {
+        const double x0 = (double)j * r;
+        const double x1 = std::min(((double)j + 1.0) * r, nd);
+        const size_t c0 = (size_t)std::min(std::floor(x0), (double)(n - 1));
+        const size_t c1 = std::max((size_t)std::min(std::ceil(x1), nd), c0 + 1);
+        const size_t count = c1 - c0;
+        ReadAxis e;
+        e.first = (uint32_t)c0; e.count = (uint32_t)count;
+        if (count == 1) { e.w_first = x1 - x0; e.w_last = 0.0; }
+        else { e.w_first = (double)(c0 + 1) - x0; e.w_last = x1 - (double)(c1 - 1); }
+        e.w_sum = (e.w_first + (double)(count > 2 ? count - 2 : 0)) + e.w_last;
+        out[j] = e;
+    }
+}
+
+bool shape_ok(size_t rows, size_t cols, size_t out_rows, size_t out_cols) {
+    return out_rows >= 1 && out_cols >= 1 && out_rows <= rows && out_cols <= cols && rows <= kReadMaxDim && cols <= kReadMaxDim;
+}
+
+// The pass over nb bands of one shape, enqueued on the context's stream (the tables are rebuilt and uploaded when the shape changes).
+int average_enqueue(sarpro_hip_ctx *ctx, const uint16_t *const d_in[], int nb, size_t rows, size_t cols, size_t in_pitch, size_t out_rows, size_t out_cols,
+                    float *const d_out[], size_t out_pitch) {
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t key[4] = {rows, cols, out_rows, out_cols};
+    const size_t tab_bytes = (out_cols + out_rows) * sizeof(ReadAxis);
+    if (!ctx->read_tab.p || std::memcmp(key, ctx->read_key, sizeof(key)) != 0) {
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); // (an earlier upload may still read the pinned stage on a stream-ordered context)
+        ctx->read_key[0] = 0;
+        HIPCHK(ctx, ctx->read_host.reserve(tab_bytes));
+        HIPCHK(ctx, ctx->read_tab.reserve(tab_bytes));
+        ReadAxis *h = ctx->read_host.as<ReadAxis>();
+        {
+            HostTimer t(ctx, "host:read_tables");
+            read_average_axis(cols, out_cols, h);
+            read_average_axis(rows, out_rows, h + out_cols);
+        }
+        HIPCHK(ctx, hipMemcpyAsync(ctx->read_tab.p, h, tab_bytes, hipMemcpyHostToDevice, ctx->stream));
+        std::memcpy(ctx->read_key, key, sizeof(key));
+    }
+    ReadArgs a{};
+    bool vec = in_pitch % 8 == 0;
+    for (int b = 0; b < nb; ++b) {
+        a.src[b] = d_in[b]; a.dst[b] = d_out[b];
+        vec = vec && (reinterpret_cast<uintptr_t>(d_in[b]) & 15) == 0;
+    }
+    a.nbands = (uint32_t)nb;
+    a.rows = (uint32_t)rows; a.cols = (uint32_t)cols; a.out_rows = (uint32_t)out_rows; a.out_cols = (uint32_t)out_cols;
+    a.in_pitch = in_pitch; a.out_pitch = out_pitch;
+    a.col_tab = ctx->read_tab.as<ReadAxis>(); a.row_tab = a.col_tab + out_cols;
+    // a strip's span of source columns fits one LDS slab where the reduction allows it (wider windows take several slabs per row)
+    const double r = (double)cols / (double)out_cols;
+    a.strip_cols = (uint32_t)std::min<double>(kReadThreads, std::max(1.0, std::floor((double)(kReadChunk - 16) / r)));
+    // about 2048 tiles (8 per compute unit), a tile no taller than the row table the kernel keeps in LDS
+    const size_t nstrips = (out_cols + a.strip_cols - 1) / a.strip_cols;
+    a.band_rows = (uint32_t)std::min<size_t>(kReadMaxBandRows, std::max<size_t>(1, out_rows * nstrips * (size_t)nb / 2048));
+    const ReadAxis *hc = ctx->read_host.as<ReadAxis>(); // (the pinned stage keeps the tables of read_key)
+    a.max_span = 0;
+    for (size_t j0 = 0; j0 < out_cols; j0 += a.strip_cols) {
+        const ReadAxis &l = hc[std::min<size_t>(j0 + a.strip_cols, out_cols) - 1];
+        a.max_span = std::max(a.max_span, l.first + l.count - (hc[j0].first & ~7u));
+    }
+    {
+        KernelTimer t(ctx, "read_average");
+        HIPCHK(ctx, launch_read_average_u16(a, vec, ctx->stream));
+    }
+    return SARPRO_HIP_OK;
+}
+
+// the shape of the flow and its filter: DEFAULT follows the rule, AVERAGE is honoured at any reduction, Lanczos is not built
+int flow_shape(sarpro_hip_ctx *ctx, size_t rows, size_t cols, int alg, size_t target_size, int pad, size_t *oc, size_t *orows, size_t *fc, size_t *fr) {
+    if (alg != SARPRO_READ_DEFAULT && alg != SARPRO_READ_AVERAGE && alg != SARPRO_READ_LANCZOS) return fail(ctx, SARPRO_HIP_ERR_INVALID_ARG, "bad read filter");
+    if (!rows || !cols || !target_size) return fail(ctx, SARPRO_HIP_ERR_INVALID_ARG, "read: rows, cols and target_size must be positive");
+    if (rows > kReadMaxDim || cols > kReadMaxDim) return fail(ctx, SARPRO_HIP_ERR_INVALID_ARG, "read: rows and cols up to 2^30");
+    int rule = 0;
+    read_dims(cols, rows, target_size, oc, orows, &rule);
+    if ((alg == SARPRO_READ_DEFAULT ? rule : alg) != SARPRO_READ_AVERAGE) {
+        char msg[200];
+        std::snprintf(msg, sizeof(msg), "read: Lanczos on read is not built (reduction %.4f: the rule picks Average from 4.0; request SARPRO_READ_AVERAGE)",
+                      std::max((double)std::max(cols, rows) / (double)target_size, 1.0));
+        return fail(ctx, SARPRO_HIP_ERR_UNSUPPORTED, msg);
+    }
+    return sarpro_hip_resize_output_dims(*oc, *orows, target_size, pad, fc, fr);
+}
+
+// device u16 bands -> the RGB raster in device memory (d_rgb: fc * fr * 3 bytes); synchronous (the resized f32 flow is)
+int flow_dev(sarpro_hip_ctx *ctx, const uint16_t *const d_bands[2], size_t rows, size_t cols, size_t in_pitch, size_t oc, size_t orows, int strategy,
+             int mode, unsigned flags, size_t target_size, int pad, uint8_t *d_rgb, sarpro_hip_resize_meta *meta) {
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t opitch = round_up(oc, 64);
+    float *d_f32[2];
+    for (int b = 0; b < 2; ++b) {
+        HIPCHK(ctx, ctx->read_band[b].reserve(orows * opitch * sizeof(float)));
+        d_f32[b] = ctx->read_band[b].as<float>();
+    }
+    RETCHK(average_enqueue(ctx, d_bands, 2, rows, cols, in_pitch, orows, oc, d_f32, opitch));
+    return sarpro_hip_dualpol_synrgb_resized_f32_dev(ctx, d_f32[0], d_f32[1], orows, oc, opitch, strategy, mode, flags, target_size, pad, d_rgb, meta);
+}
+
+// the two bands of a scene into read_src[]: host rasters, or a row reader through the pinned ring
+int stage_bands(sarpro_hip_ctx *ctx, const uint16_t *const host[2], sarpro_hip_row_reader reader, void *reader_user, size_t rows, size_t cols, size_t pitch) {
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    for (int b = 0; b < 2; ++b) {
+        HIPCHK(ctx, ctx->read_src[b].reserve(rows * pitch * sizeof(uint16_t)));
+        if (reader) {
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); // the ring's slots are free: the previous band has landed
+            RETCHK(stream_upload_band(ctx, reader, reader_user, b, rows, cols, ctx->read_src[b].as<uint16_t>(), pitch, 0));
+        } else {
+            HIPCHK(ctx, hipMemcpy2DAsync(ctx->read_src[b].p, pitch * 2, host[b], cols * 2, cols * 2, rows, hipMemcpyHostToDevice, ctx->stream));
+        }
+    }
+    return SARPRO_HIP_OK;
+}
+
+// host bands or a reader -> the RGB raster in jpeg_rgb (the raster of the context the encoder reads)
+int flow_staged(sarpro_hip_ctx *ctx, const uint16_t *const host[2], sarpro_hip_row_reader reader, void *reader_user, size_t rows, size_t cols, int alg,
+                int strategy, int mode, unsigned flags, size_t target_size, int pad, size_t *fc, size_t *fr, sarpro_hip_resize_meta *meta) {
+    size_t oc = 0, orows = 0;
+    RETCHK(flow_shape(ctx, rows, cols, alg, target_size, pad, &oc, &orows, fc, fr));
+    if (strategy < 0 || strategy > SARPRO_STRATEGY_DEFAULT) return fail(ctx, SARPRO_HIP_ERR_INVALID_ARG, "bad strategy"); // (before the scene crosses PCIe)
+    if (mode < 0 || mode > SARPRO_SYNRGB_ENHANCED) return fail(ctx, SARPRO_HIP_ERR_INVALID_ARG, "bad synrgb mode");
+    if (flags & ~SARPRO_HIP_DUALPOL_PLAIN_PIPELINE) return fail(ctx, SARPRO_HIP_ERR_INVALID_ARG, "unknown dual-pol flag");
+    const size_t pitch = round_up(cols, 64);
+    RETCHK(stage_bands(ctx, host, reader, reader_user, rows, cols, pitch));
+    HIPCHK(ctx, ctx->jpeg_rgb.reserve(std::max<size_t>(*fc * *fr * 3, 1)));
+    const uint16_t *d_bands[2] = {ctx->read_src[0].as<uint16_t>(), ctx->read_src[1].as<uint16_t>()};
+    return flow_dev(ctx, d_bands, rows, cols, pitch, oc, orows, strategy, mode, flags, target_size, pad, ctx->jpeg_rgb.as<uint8_t>(), meta);
+}
+
+int rgb_to_host(sarpro_hip_ctx *ctx, uint8_t *rgb_out, size_t bytes) {
+    if (!bytes) return SARPRO_HIP_OK;
+    HIPCHK(ctx, hipMemcpyAsync(rgb_out, ctx->jpeg_rgb.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return SARPRO_HIP_OK;
+}
+
+} // namespace
+
+extern "C" int sarpro_hip_read_output_dims(size_t cols, size_t rows, size_t target_size, size_t *out_cols, size_t *out_rows, int *alg) {
+    if (!cols || !rows || !target_size || !out_cols || !out_rows || !alg) return SARPRO_HIP_ERR_INVALID_ARG;
+    read_dims(cols, rows, target_size, out_cols, out_rows, alg);
+    return SARPRO_HIP_OK;
+}
+
+extern "C" int sarpro_hip_host_read_average_axis(size_t n_src, size_t n_dst, uint32_t first[], uint32_t count[], double w_first[], double w_last[],
+                                                 double w_sum[]) {
+    if (!n_dst || n_dst > n_src || n_src > kReadMaxDim || !first || !count || !w_first || !w_last || !w_sum) return SARPRO_HIP_ERR_INVALID_ARG;
+    std::vector<ReadAxis> tab;
+    try {
+        tab.resize(n_dst);
+    } catch (...) { // nothing may unwind across the C ABI
+        return SARPRO_HIP_ERR_OOM;
+    }
+    read_average_axis(n_src, n_dst, tab.data()); // the builder of the device tables itself
+    for (size_t j = 0; j < n_dst; ++j) {
+        first[j] = tab[j].first; count[j] = tab[j].count;
+        w_first[j] = tab[j].w_first; w_last[j] = tab[j].w_last; w_sum[j] = tab[j].w_sum;
+    }
+    return SARPRO_HIP_OK;
+}
+
+extern "C" int sarpro_hip_read_average_u16_dev(sarpro_hip_ctx *ctx, const uint16_t *d_in, size_t rows, size_t cols, size_t in_pitch, size_t out_rows,
+                                               size_t out_cols, float *d_out_f32, size_t out_pitch) {
+    if (!ctx) return SARPRO_HIP_ERR_INVALID_ARG;
+    if (!shape_ok(rows, cols, out_rows, out_cols)) return fail(ctx, SARPRO_HIP_ERR_INVALID_ARG, "read: 1 <= out_rows <= rows, 1 <= out_cols <= cols, both up to 2^30");
+    if (!d_in || !d_out_f32) return fail(ctx, SARPRO_HIP_ERR_INVALID_ARG, "null raster");
+    if (in_pitch < cols || out_pitch < out_cols) return fail(ctx, SARPRO_HIP_ERR_INVALID_ARG, "pitch < cols");
+    timing_reset(ctx);
+    const uint16_t *in[1] = {d_in};
+    float *out[1] = {d_out_f32};
+    RETCHK(average_enqueue(ctx, in, 1, rows, cols, in_pitch, out_rows, out_cols, out, out_pitch));
+    if (ctx->async_dev) { ctx->async_pending = ctx->timing; return SARPRO_HIP_OK; } // stream-ordered: nothing is read back
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return SARPRO_HIP_OK;
+}
+
+extern "C" int sarpro_hip_read_average_u16(sarpro_hip_ctx *ctx, const uint16_t *in, size_t rows, size_t cols, size_t out_rows, size_t out_cols,
+                                           float *out_f32) {
+    if (!ctx) return SARPRO_HIP_ERR_INVALID_ARG;
+    if (!shape_ok(rows, cols, out_rows, out_cols)) return fail(ctx, SARPRO_HIP_ERR_INVALID_ARG, "read: 1 <= out_rows <= rows, 1 <= out_cols <= cols, both up to 2^30");
+    if (!in || !out_f32) return fail(ctx, SARPRO_HIP_ERR_INVALID_ARG, "null raster");
+    timing_reset(ctx);
+    size_t pitch = 0;
+    RETCHK(stage_in_2d(ctx, ctx->read_src[0], in, rows, cols, 2, &pitch));
+    const size_t opitch = round_up(out_cols, 64);
+    HIPCHK(ctx, ctx->read_band[0].reserve(out_rows * opitch * sizeof(float)));
+    const uint16_t *d_in[1] = {ctx->read_src[0].as<uint16_t>()};
+    float *d_out[1] = {ctx->read_band[0].as<float>()};
+    RETCHK(average_enqueue(ctx, d_in, 1, rows, cols, pitch, out_rows, out_cols, d_out, opitch));
+    return fetch_out_2d(ctx, out_f32, d_out[0], opitch * sizeof(float), out_cols * sizeof(float), out_rows);
+}
+
+extern "C" int sarpro_hip_dualpol_synrgb_read_u16_dev(sarpro_hip_ctx *ctx, const uint16_t *d_band1, const uint16_t *d_band2, size_t rows, size_t cols,
+                                                      size_t in_pitch, int alg, int strategy, int mode, unsigned flags, size_t target_size, int pad,
+                                                      uint8_t *d_rgb_out, sarpro_hip_resize_meta *meta) {
+    if (!ctx) return SARPRO_HIP_ERR_INVALID_ARG;
+    if (!d_band1 || !d_band2 || !d_rgb_out) return fail(ctx, SARPRO_HIP_ERR_INVALID_ARG, "null raster");
+    if (in_pitch < cols) return fail(ctx, SARPRO_HIP_ERR_INVALID_ARG, "pitch < cols");
+    size_t oc = 0, orows = 0, fc = 0, fr = 0;
+    RETCHK(flow_shape(ctx, rows, cols, alg, target_size, pad, &oc, &orows, &fc, &fr));
+    TimingHold hold(ctx); // last_kernel_times: read_average and the kernels of the resized f32 flow
+    const uint16_t *d_bands[2] = {d_band1, d_band2};
+    return flow_dev(ctx, d_bands, rows, cols, in_pitch, oc, orows, strategy, mode, flags, target_size, pad, d_rgb_out, meta);
+}
+
+extern "C" int sarpro_hip_dualpol_synrgb_read_u16(sarpro_hip_ctx *ctx, const uint16_t *band1, const uint16_t *band2, size_t rows, size_t cols, int alg,
+                                                  int strategy, int mode, unsigned flags, size_t target_size, int pad, uint8_t *rgb_out,
+                                                  sarpro_hip_resize_meta *meta) {
+    if (!ctx) return SARPRO_HIP_ERR_INVALID_ARG;
+    if (!band1 || !band2 || !rgb_out) return fail(ctx, SARPRO_HIP_ERR_INVALID_ARG, "null raster");
+    TimingHold hold(ctx);
+    const uint16_t *host[2] = {band1, band2};
+    size_t fc = 0, fr = 0;
+    RETCHK(flow_staged(ctx, host, nullptr, nullptr, rows, cols, alg, strategy, mode, flags, target_size, pad, &fc, &fr, meta));
+    return rgb_to_host(ctx, rgb_out, fc * fr * 3);
+}
+
+extern "C" int sarpro_hip_dualpol_synrgb_read_stream_u16(sarpro_hip_ctx *ctx, sarpro_hip_row_reader reader, void *reader_user, size_t rows, size_t cols,
+                                                         int alg, int strategy, int mode, unsigned flags, size_t target_size, int pad, uint8_t *rgb_out,
+                                                         sarpro_hip_resize_meta *meta) {
+    if (!ctx) return SARPRO_HIP_ERR_INVALID_ARG;
+    if (!reader || !rgb_out) return fail(ctx, SARPRO_HIP_ERR_INVALID_ARG, "null reader / raster");
+    TimingHold hold(ctx);
+    const uint16_t *none[2] = {nullptr, nullptr};
+    size_t fc = 0, fr = 0;
+    RETCHK(flow_staged(ctx, none, reader, reader_user, rows, cols, alg, strategy, mode, flags, target_size, pad, &fc, &fr, meta));
+    return rgb_to_host(ctx, rgb_out, fc * fr * 3);
+}
+
+extern "C" int sarpro_hip_dualpol_synrgb_read_stream_u16_jpeg(sarpro_hip_ctx *ctx, sarpro_hip_row_reader reader, void *reader_user, size_t rows,
+                                                              size_t cols, int alg, int strategy, int mode, unsigned flags, size_t target_size, int pad,
+                                                              uint8_t *jpeg_out, size_t jpeg_capacity, size_t *jpeg_bytes_out, unsigned restart_mcus,
+                                                              sarpro_hip_resize_meta *meta) {
+    if (!ctx) return SARPRO_HIP_ERR_INVALID_ARG;
+    if (!reader || !jpeg_bytes_out || (!jpeg_out && jpeg_capacity)) return fail(ctx, SARPRO_HIP_ERR_INVALID_ARG, "null reader / buffer");
+    size_t oc = 0, orows = 0, fc = 0, fr = 0;
+    RETCHK(flow_shape(ctx, rows, cols, alg, target_size, pad, &oc, &orows, &fc, &fr)); // (before the scene crosses PCIe)
+    if (!fc || !fr || fc > 65535 || fr > 65535 || restart_mcus > 65535) return fail(ctx, SARPRO_HIP_ERR_INVALID_ARG, "jpeg: final cols and rows 1..65535, restart interval 0..65535");
+    TimingHold hold(ctx); // last_kernel_times: the average, the flow's kernels and the encoder's
+    const uint16_t *none[2] = {nullptr, nullptr};
+    RETCHK(flow_staged(ctx, none, reader, reader_user, rows, cols, alg, strategy, mode, flags, target_size, pad, &fc, &fr, meta));
+    return jpeg_encode_to_host(ctx, ctx->jpeg_rgb.as<uint8_t>(), fc, fr, fc * 3, 3, restart_mcus, jpeg_out, jpeg_capacity, jpeg_bytes_out);
+}
