@@ -541,6 +541,64 @@ int sarpro_hip_dualpol_synrgb_read_stream_u16_jpeg(sarpro_hip_ctx *ctx, sarpro_h
                                                    uint8_t *jpeg_out, size_t jpeg_capacity, size_t *jpeg_bytes_out, unsigned restart_mcus,
                                                    sarpro_hip_resize_meta *meta);
 
+/* ================= speckle filtering: Lee and Kuan over u16 and f32 bands =================
+ * The next per-pixel step SAR users expect, Phase 4 of the reference's roadmap (Lee, Kuan, Frost, Refined Lee; windows of 3-7 px;
+ * placed before autoscale).  The reference's roadmap NAMES these filters and SHIPS NONE, so THE DEFINITION IS THIS PROJECT'S OWN: it is
+ * fixed here operation by operation, the result is a function of it alone (bit for bit, whatever the tiling or pitch), and it is
+ * tested by bit pattern against the numpy restatement tests/speckleref.py.  There is no parity target beyond that.
+ *   parameters  filter = SARPRO_SPECKLE_LEE | SARPRO_SPECKLE_KUAN; window k in {3, 5, 7}, h = k / 2; looks: a finite f64 > 0.
+ *               Once per call, in f64: cu2 = 1.0 / looks; g = 1.0 / (1.0 + cu2).  cu2 is the squared coefficient of variation of the
+ *               speckle OF THE VALUES AS GIVEN: `looks` is L for L-look intensity; a caller filtering amplitude DNs passes the
+ *               equivalent number of looks for amplitude, L / 0.2732.
+ *   validity    u16: a sample is valid iff v >= 1 (DN 0 is the GRD black fill; the pipeline's mask gives the same answer).
+ *               f32: valid iff thr <= v < +inf, thr = sarpro_hip_host_f32_valid_threshold(): NaN, +-inf and everything below thr
+ *               are invalid.
+ *   window      the k x k window around (y, x), clipped to the raster: no reflection, no padding.  Only valid samples count.
+ *   per pixel   centre invalid: the output is (float)v for u16 and the input's bit pattern for f32 (the band's valid mask is
+ *               unchanged by the filter).  Otherwise, with n >= 1 valid samples in the window (the centre included):
+ *                 u16   S1 = sum v and S2 = sum v^2 as EXACT integers (any order); A = S1 * S1, D = n * S2 - A, exact integers in 64
+ *                       bits; all stay below 2^45, so (double) of each is exact.
+ *                 f32   for each window row, top to bottom, the row's partial sums left to right over its valid samples, in f64 from
+ *                       0.0: r1 = sum (double)v, r2 = sum (double)v * (double)v; S1 and S2 are the row partials added top to bottom
+ *                       from 0.0 (a row without a valid sample adds 0.0); A = S1 * S1, B = (double)n * S2, D = B - A.
+ *                 m = S1 / (double)n, one correctly rounded division.
+ *                 !(D > 0):  out = (float)m (for u16 this is exactly the centre value).
+ *                 else       q = (cu2 * A) / D;  w = 1.0 - q (Lee) or (1.0 - q) * g (Kuan);  if !(w > 0) then w = 0;
+ *                            out = (float)(m + w * ((double)v - m)).
+ *               f64 throughout, nothing contracted, one round-to-nearest-even conversion to f32.
+ *   properties  a constant raster comes back unchanged (65535 gives exactly 65535.0); out lies between m and v; a valid centre stays
+ *               valid; with very few looks w is 0 everywhere and the result is the boxcar mean of the valid samples; with very many
+ *               looks the result approaches the input.
+ * Not built: Frost, Refined Lee, windows above 7, a u16 -> u16 form, filtering inside the batch / stream / _jpeg / stripe flows. */
+typedef enum { SARPRO_SPECKLE_LEE = 0, SARPRO_SPECKLE_KUAN = 1 } sarpro_hip_speckle_filter;
+/* rows x cols samples (in_pitch elements per row) -> rows x cols f32 (out_pitch elements per row; the padding is not written), both in
+ * device memory; any shape >= 1 x 1, rasters smaller than the window included.  Stream-ordered on the context's stream and synchronous
+ * like the other _dev calls (on a SARPRO_HIP_CTX_ASYNC_DEV context it returns once enqueued).  u16: 16-byte loads when in_pitch % 8 ==
+ * 0 and d_in is 16-byte aligned (the raster is rows x in_pitch elements: the last vector of a row may reach into the row's padding,
+ * whose values are never used), element loads otherwise: the same results.  SARPRO_HIP_ERR_INVALID_ARG with a message, nothing
+ * written: a bad filter, a window not in {3, 5, 7}, looks not finite or <= 0, a pitch below cols, an empty raster, a null pointer,
+ * and for f32 an output raster that overlaps the input.  Kernel times: speckle_u16, speckle_f32. */
+int sarpro_hip_speckle_u16_dev(sarpro_hip_ctx *ctx, const uint16_t *d_in, size_t rows, size_t cols, size_t in_pitch, int filter, int window,
+                               double looks, float *d_out_f32, size_t out_pitch);
+int sarpro_hip_speckle_f32_dev(sarpro_hip_ctx *ctx, const float *d_in, size_t rows, size_t cols, size_t in_pitch, int filter, int window,
+                               double looks, float *d_out_f32, size_t out_pitch);
+/* The same with host pointers (compact rasters): the band goes up, the filtered raster comes back. */
+int sarpro_hip_speckle_u16(sarpro_hip_ctx *ctx, const uint16_t *in, size_t rows, size_t cols, int filter, int window, double looks,
+                           float *out_f32);
+int sarpro_hip_speckle_f32(sarpro_hip_ctx *ctx, const float *in, size_t rows, size_t cols, int filter, int window, double looks,
+                           float *out_f32);
+/* "Two measurement bands in, filtered at native resolution, RGB out": both bands filtered (one launch) into f32 rasters of the
+ * context, then sarpro_hip_dualpol_synrgb_resized_f32_dev on them, unchanged, with the caller's strategy, mode, flags
+ * (SARPRO_HIP_DUALPOL_PLAIN_PIPELINE or 0), target_size (0 = native size) and pad.  d_rgb_out: final_rows * final_cols * 3 bytes,
+ * (final_cols, final_rows) = sarpro_hip_resize_output_dims(cols, rows, target_size, pad).  Synchronous.  No other entry point filters. */
+int sarpro_hip_dualpol_synrgb_speckle_u16_dev(sarpro_hip_ctx *ctx, const uint16_t *d_band1, const uint16_t *d_band2, size_t rows, size_t cols,
+                                              size_t in_pitch, int filter, int window, double looks, int strategy, int mode, unsigned flags,
+                                              size_t target_size, int pad, uint8_t *d_rgb_out, sarpro_hip_resize_meta *meta);
+/* Host u16 bands in (compact), host RGB out. */
+int sarpro_hip_dualpol_synrgb_speckle_u16(sarpro_hip_ctx *ctx, const uint16_t *band1, const uint16_t *band2, size_t rows, size_t cols,
+                                          int filter, int window, double looks, int strategy, int mode, unsigned flags, size_t target_size,
+                                          int pad, uint8_t *rgb_out, sarpro_hip_resize_meta *meta);
+
 /* ---- file shims for the two callbacks: uncompressed strip TIFF / BigTIFF (what Sentinel-1 GRD measurement rasters
  * are; io/gdal.rs:107-141 and io/writers/tiff.rs:6-78 go through GDAL).  Baseline TIFF 6.0 + BigTIFF, II or MM,
  * Compression = 1, strips, 8- / 16-bit unsigned samples, chunky or planar; anything else fails with

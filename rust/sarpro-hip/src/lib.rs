@@ -54,6 +54,11 @@ pub mod types {
     #[derive(Copy, Clone, PartialEq, Eq, PartialOrd, Ord, Debug, Hash)]
     pub enum OutputFormat { TIFF, JPEG }
 
+    /// `sarpro_hip_speckle_filter`: this library's own (the reference's roadmap names the filters and ships none)
+    #[repr(i32)]
+    #[derive(Copy, Clone, PartialEq, Eq, PartialOrd, Ord, Debug, Hash)]
+    pub enum SpeckleFilter { Lee = 0, Kuan = 1 }
+
     /// types.rs:40-45
     #[derive(Copy, Clone, PartialEq, Eq, Debug)]
     pub enum ProcessingOperation { SingleBand, MultibandVvVh, MultibandHhHv, PolarOp(PolarizationOperation) }
@@ -74,7 +79,7 @@ pub mod types {
         }
     }
 }
-pub use types::{AutoscaleStrategy, BitDepth, OutputFormat, PolarizationOperation, ProcessingOperation, SyntheticRgbMode};
+pub use types::{AutoscaleStrategy, BitDepth, OutputFormat, PolarizationOperation, ProcessingOperation, SpeckleFilter, SyntheticRgbMode};
 
 /// What a sarpro integration maps onto `Error::Processing` (src/error.rs:39-46).
 #[derive(Debug, Clone)]
@@ -460,6 +465,71 @@ impl RasterCore {
             syn_mode as c_int, flags, target_size, pad as c_int, rgb.as_mut_ptr(), &mut meta) })?;
         Ok(ProcessedImage { width: fc, height: fr, bit_depth: BitDepth::U8, format: OutputFormat::JPEG, gray: None, gray16: None,
             rgb: Some(rgb), gray_band2: None, gray16_band2: None, resize: meta })
+    }
+
+    // ------------------------------------------------------------------ speckle filtering (this library's own definition)
+    /// Lee / Kuan over a u16 band with a window of 3, 5 or 7 -> f32 of the same shape.  `looks`: the equivalent number of looks of the
+    /// values as given (amplitude DNs: L / 0.2732).  A caller of the reference would place this between the band read and
+    /// `process_scalar_data_pipeline`.
+    pub fn try_speckle_filter_u16(&self, band: &Array2<u16>, filter: SpeckleFilter, window: usize, looks: f64) -> Result<Array2<f32>> {
+        let (rows, cols) = band.dim();
+        let b = band.as_standard_layout();
+        let mut out = vec![0f32; rows * cols];
+        self.chk(unsafe { sys::sarpro_hip_speckle_u16(self.ctx, b.as_ptr(), rows, cols, filter as c_int, window as c_int, looks, out.as_mut_ptr()) })?;
+        Array2::from_shape_vec((rows, cols), out)
+            .map_err(|_| HipError { code: sys::SARPRO_HIP_ERR_SHAPE_MISMATCH, message: "output shape".into() })
+    }
+
+    /// The same for an f32 band (valid: threshold <= v < +inf; an invalid centre keeps its bit pattern).
+    pub fn try_speckle_filter_f32(&self, band: &Array2<f32>, filter: SpeckleFilter, window: usize, looks: f64) -> Result<Array2<f32>> {
+        let (rows, cols) = band.dim();
+        let b = band.as_standard_layout();
+        let mut out = vec![0f32; rows * cols];
+        self.chk(unsafe { sys::sarpro_hip_speckle_f32(self.ctx, b.as_ptr(), rows, cols, filter as c_int, window as c_int, looks, out.as_mut_ptr()) })?;
+        Array2::from_shape_vec((rows, cols), out)
+            .map_err(|_| HipError { code: sys::SARPRO_HIP_ERR_SHAPE_MISMATCH, message: "output shape".into() })
+    }
+
+    /// Both u16 bands filtered at native resolution (one launch), then the resized f32 flow on the filtered bands (api/mod.rs:404-437
+    /// when `plain_pipeline`, save.rs:317-367 otherwise): per-band u8, resize to `target_size` (None: native size), pad, synRGB.
+    pub fn try_render_multiband_image_speckle_u16(&self, band1: &Array2<u16>, band2: &Array2<u16>, filter: SpeckleFilter, window: usize, looks: f64,
+        target_size: Option<usize>, pad: bool, autoscale: AutoscaleStrategy, syn_mode: SyntheticRgbMode, plain_pipeline: bool) -> Result<ProcessedImage> {
+        if band1.dim() != band2.dim() {
+            return Err(HipError { code: sys::SARPRO_HIP_ERR_SHAPE_MISMATCH, message: "band shapes differ".into() });
+        }
+        let (rows, cols) = band1.dim();
+        let (b1, b2) = (band1.as_standard_layout(), band2.as_standard_layout());
+        let (mut fc, mut fr) = (0usize, 0usize);
+        let ts = target_size.unwrap_or(0);
+        self.chk(unsafe { sys::sarpro_hip_resize_output_dims(cols, rows, ts, pad as c_int, &mut fc, &mut fr) })?;
+        let flags = if plain_pipeline { sys::SARPRO_HIP_DUALPOL_PLAIN_PIPELINE } else { 0 };
+        let mut rgb = vec![0u8; fc * fr * 3];
+        let mut meta = zeroed_meta();
+        self.chk(unsafe { sys::sarpro_hip_dualpol_synrgb_speckle_u16(self.ctx, b1.as_ptr(), b2.as_ptr(), rows, cols, filter as c_int, window as c_int,
+            looks, autoscale as c_int, syn_mode as c_int, flags, ts, pad as c_int, rgb.as_mut_ptr(), &mut meta) })?;
+        Ok(ProcessedImage { width: fc, height: fr, bit_depth: BitDepth::U8, format: OutputFormat::JPEG, gray: None, gray16: None,
+            rgb: Some(rgb), gray_band2: None, gray16_band2: None, resize: meta })
+    }
+
+    /// Device-resident forms (`d_*` are device addresses; pitches in elements; the f32 form's output may not overlap its input).
+    pub unsafe fn dev_speckle_u16(&self, d_in: *const u16, rows: usize, cols: usize, in_pitch: usize, filter: SpeckleFilter, window: usize, looks: f64,
+        d_out: *mut f32, out_pitch: usize) -> Result<()> {
+        self.chk(sys::sarpro_hip_speckle_u16_dev(self.ctx, d_in, rows, cols, in_pitch, filter as c_int, window as c_int, looks, d_out, out_pitch))
+    }
+
+    pub unsafe fn dev_speckle_f32(&self, d_in: *const f32, rows: usize, cols: usize, in_pitch: usize, filter: SpeckleFilter, window: usize, looks: f64,
+        d_out: *mut f32, out_pitch: usize) -> Result<()> {
+        self.chk(sys::sarpro_hip_speckle_f32_dev(self.ctx, d_in, rows, cols, in_pitch, filter as c_int, window as c_int, looks, d_out, out_pitch))
+    }
+
+    pub unsafe fn dev_dualpol_synrgb_speckle_u16(&self, d_band1: *const u16, d_band2: *const u16, rows: usize, cols: usize, in_pitch: usize,
+        filter: SpeckleFilter, window: usize, looks: f64, strategy: AutoscaleStrategy, mode: SyntheticRgbMode, plain_pipeline: bool,
+        target_size: Option<usize>, pad: bool, d_rgb: *mut u8) -> Result<ResizeMeta> {
+        let flags = if plain_pipeline { sys::SARPRO_HIP_DUALPOL_PLAIN_PIPELINE } else { 0 };
+        let mut meta = zeroed_meta();
+        self.chk(sys::sarpro_hip_dualpol_synrgb_speckle_u16_dev(self.ctx, d_band1, d_band2, rows, cols, in_pitch, filter as c_int, window as c_int,
+            looks, strategy as c_int, mode as c_int, flags, target_size.unwrap_or(0), pad as c_int, d_rgb, &mut meta))?;
+        Ok(meta)
     }
 
     // ------------------------------------------------------------------ device-pointer entry points (rasters resident in HBM)

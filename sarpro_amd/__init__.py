@@ -4,7 +4,7 @@ Product code: HIP kernels + C ABI in csrc/ (libsarpro_hip.so) and this thin host
 mirror of the reference interface.  No CPU fallback; the oracle under oracle/ is test
 infrastructure and is never imported from here.
 """
-from .types import AutoscaleStrategy, BitDepth, PolarizationOperation, SyntheticRgbMode  # noqa: F401
+from .types import AutoscaleStrategy, BitDepth, PolarizationOperation, SpeckleFilter, SyntheticRgbMode  # noqa: F401
 from .api import (LocalGroup, Context, SarproHipError, Stripe, StripeF32, host_f32_merge_partials, comm_unique_id, host_clahe_bin_lut_u16,  # noqa: F401
                   host_clahe_cdfs, host_clahe_saturated_levels, host_clahe_shape_ok, host_level_lut_u16, host_stats_from_dn_hist,
                   host_stripe_plan, host_stripe_resized_rows, host_synrgb_luts, host_u8_rescale_lut, host_window,

@@ -18,6 +18,7 @@ ERR_HIP, ERR_RCCL, ERR_OOM, ERR_NO_DEVICE, ERR_IO = -4, -5, -6, -7, -8
 ERR_BUFFER_TOO_SMALL = -9
 ERR_UNSUPPORTED = -10
 READ_DEFAULT, READ_AVERAGE, READ_LANCZOS = -1, 0, 1  # sarpro_hip_read_alg
+SPECKLE_LEE, SPECKLE_KUAN = 0, 1  # sarpro_hip_speckle_filter
 
 
 class Stats(C.Structure):
@@ -116,6 +117,8 @@ SYMBOLS = [
     "sarpro_hip_read_output_dims", "sarpro_hip_host_read_average_axis", "sarpro_hip_read_average_u16_dev", "sarpro_hip_read_average_u16",
     "sarpro_hip_dualpol_synrgb_read_u16_dev", "sarpro_hip_dualpol_synrgb_read_u16", "sarpro_hip_dualpol_synrgb_read_stream_u16",
     "sarpro_hip_dualpol_synrgb_read_stream_u16_jpeg",
+    "sarpro_hip_speckle_u16_dev", "sarpro_hip_speckle_f32_dev", "sarpro_hip_speckle_u16", "sarpro_hip_speckle_f32",
+    "sarpro_hip_dualpol_synrgb_speckle_u16_dev", "sarpro_hip_dualpol_synrgb_speckle_u16",
 ]
 
 if not os.path.exists(LIB_PATH):
@@ -295,3 +298,10 @@ _proto("sarpro_hip_dualpol_synrgb_read_u16_dev", _i, _vp, _vp, _vp, _sz, _sz, _s
 _proto("sarpro_hip_dualpol_synrgb_read_u16", _i, _vp, _vp, _vp, _sz, _sz, _i, _i, _i, _u, _sz, _i, _vp, _M)
 _proto("sarpro_hip_dualpol_synrgb_read_stream_u16", _i, _vp, _vp, _vp, _sz, _sz, _i, _i, _i, _u, _sz, _i, _vp, _M)
 _proto("sarpro_hip_dualpol_synrgb_read_stream_u16_jpeg", _i, _vp, _vp, _vp, _sz, _sz, _i, _i, _i, _u, _sz, _i, _vp, _sz, C.POINTER(_sz), _u, _M)
+_d = C.c_double
+for _n in ("sarpro_hip_speckle_u16_dev", "sarpro_hip_speckle_f32_dev"):
+    _proto(_n, _i, _vp, _vp, _sz, _sz, _sz, _i, _i, _d, _vp, _sz)
+for _n in ("sarpro_hip_speckle_u16", "sarpro_hip_speckle_f32"):
+    _proto(_n, _i, _vp, _vp, _sz, _sz, _i, _i, _d, _vp)
+_proto("sarpro_hip_dualpol_synrgb_speckle_u16_dev", _i, _vp, _vp, _vp, _sz, _sz, _sz, _i, _i, _d, _i, _i, _u, _sz, _i, _vp, _M)
+_proto("sarpro_hip_dualpol_synrgb_speckle_u16", _i, _vp, _vp, _vp, _sz, _sz, _i, _i, _d, _i, _i, _u, _sz, _i, _vp, _M)

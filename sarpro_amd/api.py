@@ -23,7 +23,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import F32Partial, Stats, lib
-from .types import AutoscaleStrategy, BitDepth, PolarizationOperation, SyntheticRgbMode
+from .types import AutoscaleStrategy, BitDepth, PolarizationOperation, SpeckleFilter, SyntheticRgbMode
 
 
 class SarproHipError(RuntimeError):
@@ -473,6 +473,55 @@ class Context:
         m = ResizeMeta()
         self._chk(lib.sarpro_hip_dualpol_synrgb_read_u16_dev(self._h, _vp(d_b1), _vp(d_b2), rows, cols, in_pitch, int(alg), int(strategy), int(mode),
                                                              1 if plain_pipeline else 0, target_size, int(pad), _vp(d_rgb), C.byref(m)))
+        return m
+
+    # ------------------------------------------------------------------ speckle filtering (this library's own definition: DESIGN.md 9c)
+    def speckle(self, band: np.ndarray, filter: SpeckleFilter, window: int, looks: float) -> np.ndarray:
+        """Lee / Kuan over a (rows, cols) uint16 or float32 band with a window of 3, 5 or 7 -> float32 of the same shape.  `looks` is the
+        equivalent number of looks of the values as given (amplitude DNs: L / 0.2732)."""
+        if band.dtype == np.uint16:
+            b, fn = np.ascontiguousarray(band), lib.sarpro_hip_speckle_u16
+        elif band.dtype == np.float32:
+            b, fn = np.ascontiguousarray(band), lib.sarpro_hip_speckle_f32
+        else:
+            raise ValueError("band must be uint16 or float32")
+        rows, cols = b.shape
+        out = np.empty((rows, cols), np.float32)
+        self._chk(fn(self._h, _vp(b), rows, cols, int(filter), int(window), float(looks), _vp(out)))
+        return out
+
+    def dev_speckle_u16(self, d_in: int, rows: int, cols: int, in_pitch: int, filter, window: int, looks: float, d_out: int, out_pitch: int):
+        """speckle with the u16 band (in_pitch elements per row) and the f32 raster (out_pitch elements per row) in device memory."""
+        self._chk(lib.sarpro_hip_speckle_u16_dev(self._h, _vp(d_in), rows, cols, in_pitch, int(filter), int(window), float(looks), _vp(d_out), out_pitch))
+
+    def dev_speckle_f32(self, d_in: int, rows: int, cols: int, in_pitch: int, filter, window: int, looks: float, d_out: int, out_pitch: int):
+        """The same for an f32 band; the output raster may not overlap the input."""
+        self._chk(lib.sarpro_hip_speckle_f32_dev(self._h, _vp(d_in), rows, cols, in_pitch, int(filter), int(window), float(looks), _vp(d_out), out_pitch))
+
+    def dualpol_synrgb_speckle(self, band1: np.ndarray, band2: np.ndarray, filter, window: int, looks: float, strategy: AutoscaleStrategy,
+                               target_size: int | None, pad: bool, mode: SyntheticRgbMode = SyntheticRgbMode.Default, plain_pipeline: bool = False):
+        """Two u16 bands -> both filtered at native resolution -> dualpol_synrgb_resized_f32 on the filtered f32 bands
+        -> ((final_rows, final_cols, 3) RGB, ResizeMeta).  target_size None / 0: native size."""
+        from ._lib import ResizeMeta
+        rows, cols = band1.shape
+        fc, fr = resize_output_dims(cols, rows, target_size, pad)
+        rgb = np.empty((fr, fc, 3), np.uint8)
+        m = ResizeMeta()
+        b1 = np.ascontiguousarray(band1, np.uint16)
+        b2 = np.ascontiguousarray(band2, np.uint16)
+        self._chk(lib.sarpro_hip_dualpol_synrgb_speckle_u16(self._h, _vp(b1), _vp(b2), rows, cols, int(filter), int(window), float(looks), int(strategy),
+                                                            int(mode), 1 if plain_pipeline else 0, target_size or 0, int(pad), _vp(rgb), C.byref(m)))
+        return rgb, m
+
+    def dev_dualpol_synrgb_speckle(self, d_b1: int, d_b2: int, rows: int, cols: int, in_pitch: int, filter, window: int, looks: float,
+                                   strategy: AutoscaleStrategy, target_size: int | None, pad: bool, d_rgb: int,
+                                   mode: SyntheticRgbMode = SyntheticRgbMode.Default, plain_pipeline: bool = False):
+        """dualpol_synrgb_speckle with the bands and the compact final_rows x final_cols x 3 RGB raster in device memory."""
+        from ._lib import ResizeMeta
+        m = ResizeMeta()
+        self._chk(lib.sarpro_hip_dualpol_synrgb_speckle_u16_dev(self._h, _vp(d_b1), _vp(d_b2), rows, cols, in_pitch, int(filter), int(window),
+                                                                float(looks), int(strategy), int(mode), 1 if plain_pipeline else 0,
+                                                                target_size or 0, int(pad), _vp(d_rgb), C.byref(m)))
         return m
 
     def dualpol_synrgb_read_stream(self, reader, rows: int, cols: int, strategy, target_size: int, pad: bool, mode=SyntheticRgbMode.Default,

@@ -235,6 +235,7 @@ struct sarpro_hip_ctx {
     sarpro::DevBuf read_tab, read_src[2], read_band[2];
     sarpro::PinnedBuf read_host;
     size_t read_key[4] = {0, 0, 0, 0};
+    sarpro::DevBuf speckle_band[2];              // speckle filtering (speckle_path.cpp): the filtered f32 rasters of the host forms and the flows
     sarpro::DevBuf chain_consts;                 // device-resident chain: dB table | suppressed lut_r/g per floor | blue pairs
     sarpro::DevBuf chain_scratch;               // statistics step: per-slice partials | 4096 bins per band
     sarpro::DevBuf chain_state;                  // ChainBandState[2] | resc[2][256] | identity[2] | floor

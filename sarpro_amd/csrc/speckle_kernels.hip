@@ -1,0 +1,270 @@
+// speckle_kernels.hip -- adaptive speckle filters (Lee, Kuan) over u16 and f32 bands, f32 out: DESIGN.md 9c.  The definition is this
+// project's own -- the reference's roadmap names the filters (ROADMAP Phase 4) and ships none -- and is fixed operation by operation:
+//   window   k x k around the pixel, clipped to the raster, only VALID samples count (u16: v >= 1; f32: thr <= v < +inf)
+//   centre invalid: the output is (float)v (u16) / the input's bit pattern (f32)
+//   otherwise, n valid samples:  S1 = sum v, S2 = sum v^2;  A = S1 * S1;  D = n * S2 - A;  m = S1 / n;
+//            !(D > 0): out = (float)m;   else q = (cu2 * A) / D;  w = 1 - q (Lee) | (1 - q) * g (Kuan);  !(w > 0): w = 0;
+//            out = (float)(m + w * (v - m))
+//   u16: S1, S2, A, D are EXACT integers (any order; all below 2^45, so their f64 forms are exact).  f32: per window row, top to bottom,
+//   the row's partial sums left to right in f64 from 0.0, the row partials added top to bottom from 0.0; B = (double)n * S2; D = B - A.
+//   f64 throughout, nothing contracted (-ffp-contract=off), correctly rounded divisions, one rounding to f32.  Lee is computed as
+//   (1 - q) * 1.0, which is 1 - q bit for bit.
+// So the result is a function of the definition alone, whatever the tiling, the pitch or the load width.
+//
+// k_speckle_u16 (the hot path: 400 MP bands, 2 B/px in, 4 B/px out).  A workgroup owns a strip of <= 256 output columns (one lane each)
+// x a band of output rows; it walks the band's source rows (h halo rows above and below; rows and columns outside the raster read as 0 =
+// invalid) top to bottom through two LDS stages of 28 / 30 rows x (256 + 2 * 8) samples: while the lanes work through stage s, the four
+// 16-byte loads per lane of stage s + 1 are in flight into registers and are written to the other half behind the compiler's counted
+// wait, one barrier per stage.  Per source row a lane forms the row's horizontal (n, S1, S2) over its k columns from LDS, pushes it into
+// a ring of k row entries in registers (statically indexed: the row loop is unrolled by k, and a stage holds a multiple of k rows), keeps
+// the vertical totals by adding the new row and subtracting the oldest -- exact, these are integers -- and emits the pixel of row y - h.
+// A ring entry is 3 words: S1 | n << 19, and S2 (< 2^35) with the row's centre sample in bits 40..55.
+#include "speckle_kernels.h"
+
+namespace sarpro {
+
+namespace {
+
+// the f64 tail both flavours share; nd >= 1
+__device__ __forceinline__ float speckle_tail(double nd, double S1, double A, double D, double vd, double cu2, double g) {
+    const double m = S1 / nd;
+    const double q = (cu2 * A) / D;
+    double w = (1.0 - q) * g;
+    w = w > 0.0 ? w : 0.0;
+    const double o = m + w * (vd - m);
+    return D > 0.0 ? (float)o : (float)m;
+}
+
+// 8 samples from column c (a multiple of 8, 0 <= c < cols) of a row.  The vector form may read the row's padding (c + 8 <= in_pitch,
+// a multiple of 8); the caller zeroes the samples at and beyond `cols`.  The element form reads them as 0.
+template <bool VEC>
+__device__ __forceinline__ uint4 speckle_fetch8(const uint16_t *row, uint32_t c, uint32_t cols) {
+    if (VEC) return *reinterpret_cast<const uint4 *>(row + c);
+    uint32_t w[4];
+#pragma unroll
+    for (uint32_t p = 0; p < 4; ++p) {
+        const uint32_t lo = c + 2 * p < cols ? row[c + 2 * p] : 0u;
+        const uint32_t hi = c + 2 * p + 1 < cols ? row[c + 2 * p + 1] : 0u;
+        w[p] = lo | (hi << 16);
+    }
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+// word p of a vector of which the first nv samples (0..8) lie inside the raster
+__device__ __forceinline__ uint32_t speckle_keep(uint32_t w, uint32_t nv, uint32_t p) {
+    return nv >= 2 * p + 2 ? w : (nv == 2 * p + 1 ? (w & 0xffffu) : 0u);
+}
+
+} // namespace
+
+template <uint32_t K, bool VEC>
+__global__ __launch_bounds__(kSpeckleThreads) void k_speckle_u16(SpeckleArgs a) {
+    constexpr uint32_t H = K / 2;
+    constexpr uint32_t ROWS = K == 7 ? 28u : 30u;              // source rows of a stage: a multiple of K
+    constexpr uint32_t VPR = kSpeckleRowLen / 8;               // 16-byte vectors of a stage row (34)
+    constexpr uint32_t NVEC = ROWS * VPR;
+    constexpr uint32_t LOADS = (NVEC + kSpeckleThreads - 1) / kSpeckleThreads; // 4
+    static_assert(ROWS % K == 0, "a stage starts at ring entry 0");
+    static_assert(H <= kSpeckleHaloCols && kSpeckleRowLen % 8 == 0, "the halo is a whole vector");
+    __shared__ uint4 s_stage[2][NVEC];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t nstrips = (a.cols + kSpeckleThreads - 1) / kSpeckleThreads;
+    const uint32_t nrb = (a.rows + a.band_rows - 1) / a.band_rows;
+    uint32_t t = blockIdx.x; // strips fastest: neighbouring workgroups read neighbouring spans of the same source rows
+    const uint32_t strip = t % nstrips;
+    t /= nstrips;
+    const uint32_t rb = t % nrb, band = t / nrb;
+    const uint16_t *src = static_cast<const uint16_t *>(band ? a.src[1] : a.src[0]);
+    float *dst = band ? a.dst[1] : a.dst[0];
+    const uint32_t x0 = strip * kSpeckleThreads;
+    const uint32_t i0 = rb * a.band_rows, i1 = min(i0 + a.band_rows, a.rows);
+    // source rows [ys, ye) of the band, halo included; rows outside the raster are all invalid
+    const int32_t ys = (int32_t)i0 - (int32_t)H, ye = (int32_t)i1 + (int32_t)H;
+    const uint32_t nstages = ((uint32_t)(ye - ys) + ROWS - 1) / ROWS;
+    const bool active = x0 + tid < a.cols;
+    // the lane's vectors of a stage: vector v = tid + q * 256 is vector v % VPR of stage row v / VPR (the same for every stage)
+    uint32_t lrow[LOADS], lcol[LOADS], lnv[LOADS];
+#pragma unroll
+    for (uint32_t q = 0; q < LOADS; ++q) {
+        const uint32_t v = tid + q * kSpeckleThreads;
+        lrow[q] = v / VPR;
+        const int32_t c = (int32_t)x0 - (int32_t)kSpeckleHaloCols + (int32_t)(v % VPR) * 8;
+        const bool ok = v < NVEC && c >= 0 && (uint32_t)c < a.cols;
+        lcol[q] = ok ? (uint32_t)c : 0u;
+        lnv[q] = ok ? min(8u, a.cols - (uint32_t)c) : 0u;
+    }
+    uint4 regs[LOADS];
+    auto load_stage = [&](uint32_t s) {
+#pragma unroll
+        for (uint32_t q = 0; q < LOADS; ++q) {
+            const int32_t y = ys + (int32_t)(s * ROWS + lrow[q]);
+            regs[q] = make_uint4(0u, 0u, 0u, 0u);
+            if (lnv[q] && y >= 0 && y < ye && (uint32_t)y < a.rows) regs[q] = speckle_fetch8<VEC>(src + (size_t)y * a.in_pitch, lcol[q], a.cols);
+        }
+    };
+    auto write_stage = [&](uint32_t half) {
+#pragma unroll
+        for (uint32_t q = 0; q < LOADS; ++q) {
+            const uint32_t v = tid + q * kSpeckleThreads;
+            const uint4 r = regs[q];
+            if (v < NVEC)
+                s_stage[half][v] = make_uint4(speckle_keep(r.x, lnv[q], 0), speckle_keep(r.y, lnv[q], 1), speckle_keep(r.z, lnv[q], 2), speckle_keep(r.w, lnv[q], 3));
+        }
+    };
+    load_stage(0);
+    write_stage(0);
+    __syncthreads();
+    // the ring of the last K rows (entry r = rows with (y - ys) % K == r) and the window's totals
+    uint32_t e1[K];
+    uint64_t e2[K];
+#pragma unroll
+    for (uint32_t r = 0; r < K; ++r) { e1[r] = 0u; e2[r] = 0ull; }
+    uint32_t tn = 0, ts1 = 0;
+    uint64_t ts2 = 0;
+    constexpr uint64_t kS2Mask = (1ull << 40) - 1;
+    for (uint32_t s = 0; s < nstages; ++s) {
+        const bool more = s + 1 < nstages;
+        if (more) load_stage(s + 1);
+        const uint16_t *lds = reinterpret_cast<const uint16_t *>(&s_stage[s & 1][0]) + tid + kSpeckleHaloCols - H;
+        int32_t y = ys + (int32_t)(s * ROWS);
+        for (uint32_t g = 0; g < ROWS / K && y < ye; ++g) {
+#pragma unroll
+            for (uint32_t r = 0; r < K; ++r, ++y) {
+                if (y >= ye) break; // (uniform)
+                const uint16_t *p = lds + (g * K + r) * kSpeckleRowLen;
+                const uint32_t c = p[H];
+                uint32_t n = c != 0u, s1 = c;
+                uint64_t s2 = c * c; // (c < 2^16: the 32-bit product is the whole one)
+#ifndef SARPRO_SPECKLE_ABLATE_SUM // (timing variant: the pass without the window's LDS reads and row sums -- a window of k rows x 1 column)
+#pragma unroll
+                for (uint32_t j = 0; j < K; ++j) {
+                    if (j == H) continue;
+                    const uint32_t v = p[j];
+                    n += v != 0u;
+                    s1 += v;
+                    s2 += v * v;
+                }
+#endif
+                tn = tn + n - (e1[r] >> 19);
+                ts1 = ts1 + s1 - (e1[r] & 0x7ffffu);
+                ts2 = ts2 + s2 - (e2[r] & kS2Mask);
+                e1[r] = s1 | (n << 19);
+                e2[r] = s2 | ((uint64_t)c << 40);
+                const int32_t yo = y - (int32_t)H; // the output row whose window this row completes
+                if (yo < (int32_t)i0) continue;    // (uniform)
+                const uint32_t v = (uint32_t)(e2[(r + K - H) % K] >> 40);
+                float out;
+#ifndef SARPRO_SPECKLE_ABLATE_TAIL // (timing variant: the pass without its f64 tail)
+                const uint64_t A = (uint64_t)ts1 * ts1;
+                const uint64_t D = (uint64_t)tn * ts2 - A;
+                out = speckle_tail((double)max(tn, 1u), (double)ts1, (double)A, (double)D, (double)v, a.cu2, a.g);
+#else
+                out = (float)(ts1 + tn + (uint32_t)ts2);
+#endif
+                out = v ? out : 0.0f;
+                if (active) dst[(size_t)yo * a.out_pitch + x0 + tid] = out;
+            }
+        }
+        if (more) write_stage((s + 1) & 1);
+        __syncthreads();
+    }
+}
+
+// The f32 flavour: the same strips and row bands, one tile of (16 + 2h) x (256 + 2h) samples in LDS (outside the raster: NaN = invalid);
+// a lane sums its window's rows from LDS in the order of the definition.  The f32 scenes this library sees are a few MP.
+template <uint32_t K>
+__global__ __launch_bounds__(kSpeckleThreads) void k_speckle_f32(SpeckleArgs a) {
+    constexpr uint32_t H = K / 2, TR = kSpeckleF32BandRows, LR = TR + 2 * H, LC = kSpeckleThreads + 2 * H;
+    __shared__ uint32_t s_tile[LR][LC];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t nstrips = (a.cols + kSpeckleThreads - 1) / kSpeckleThreads;
+    const uint32_t nrb = (a.rows + TR - 1) / TR;
+    uint32_t t = blockIdx.x;
+    const uint32_t strip = t % nstrips;
+    t /= nstrips;
+    const uint32_t rb = t % nrb, band = t / nrb;
+    const uint32_t *src = static_cast<const uint32_t *>(band ? a.src[1] : a.src[0]); // (bit patterns: an invalid centre goes out as it came in)
+    uint32_t *dst = reinterpret_cast<uint32_t *>(band ? a.dst[1] : a.dst[0]);
+    const uint32_t x0 = strip * kSpeckleThreads;
+    const uint32_t i0 = rb * TR, i1 = min(i0 + TR, a.rows);
+    for (uint32_t idx = tid; idx < LR * LC; idx += kSpeckleThreads) {
+        const uint32_t r = idx / LC, c = idx % LC;
+        const int32_t y = (int32_t)i0 - (int32_t)H + (int32_t)r, x = (int32_t)x0 - (int32_t)H + (int32_t)c;
+        uint32_t bits = 0x7fc00000u;
+        if (y >= 0 && (uint32_t)y < a.rows && x >= 0 && (uint32_t)x < a.cols) bits = src[(size_t)y * a.in_pitch + (uint32_t)x];
+        s_tile[r][c] = bits;
+    }
+    __syncthreads();
+    const bool active = x0 + tid < a.cols;
+    const float thr = a.thr, inf = __builtin_inff();
+    for (uint32_t i = i0; i < i1; ++i) {
+        double S1 = 0.0, S2 = 0.0;
+        uint32_t n = 0;
+#pragma unroll
+        for (uint32_t dy = 0; dy < K; ++dy) {
+            double r1 = 0.0, r2 = 0.0;
+#pragma unroll
+            for (uint32_t dx = 0; dx < K; ++dx) {
+                const float v = __uint_as_float(s_tile[i - i0 + dy][tid + dx]);
+                const bool ok = v >= thr && v < inf;
+                const double d = ok ? (double)v : 0.0; // (adding 0.0 to these non-negative sums changes nothing)
+                r1 = r1 + d;
+                r2 = r2 + d * d;
+                n += ok;
+            }
+            S1 = S1 + r1;
+            S2 = S2 + r2;
+        }
+        const uint32_t cbits = s_tile[i - i0 + H][tid + H];
+        const float cv = __uint_as_float(cbits);
+        const bool cok = cv >= thr && cv < inf;
+        const double A = S1 * S1;
+        const double B = (double)n * S2;
+        const double D = B - A;
+        const float out = speckle_tail((double)max(n, 1u), S1, A, D, cok ? (double)cv : 0.0, a.cu2, a.g);
+        const uint32_t obits = cok ? __float_as_uint(out) : cbits;
+        if (active) dst[(size_t)i * a.out_pitch + x0 + tid] = obits;
+    }
+}
+
+namespace {
+
+uint64_t speckle_grid(const SpeckleArgs &a, uint32_t band_rows) {
+    const uint64_t nstrips = (a.cols + kSpeckleThreads - 1) / kSpeckleThreads, nrb = (a.rows + band_rows - 1) / band_rows;
+    return nstrips * nrb * a.nbands;
+}
+
+} // namespace
+
+hipError_t launch_speckle_u16(const SpeckleArgs &a, int window, bool vec, hipStream_t s) {
+    if (!a.band_rows || a.band_rows > kSpeckleMaxBandRows || !a.rows || !a.cols || a.rows > kSpeckleMaxDim || a.cols > kSpeckleMaxDim) return hipErrorInvalidValue;
+    const uint64_t grid = speckle_grid(a, a.band_rows);
+    if (!grid || grid > 0x7fffffffull) return hipErrorInvalidValue;
+    const dim3 g((unsigned)grid), b(kSpeckleThreads);
+    switch (window * 2 + (vec ? 1 : 0)) {
+    case 6: hipLaunchKernelGGL((k_speckle_u16<3, false>), g, b, 0, s, a); break;
+    case 7: hipLaunchKernelGGL((k_speckle_u16<3, true>), g, b, 0, s, a); break;
+    case 10: hipLaunchKernelGGL((k_speckle_u16<5, false>), g, b, 0, s, a); break;
+    case 11: hipLaunchKernelGGL((k_speckle_u16<5, true>), g, b, 0, s, a); break;
+    case 14: hipLaunchKernelGGL((k_speckle_u16<7, false>), g, b, 0, s, a); break;
+    case 15: hipLaunchKernelGGL((k_speckle_u16<7, true>), g, b, 0, s, a); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_speckle_f32(const SpeckleArgs &a, int window, hipStream_t s) {
+    if (!a.rows || !a.cols || a.rows > kSpeckleMaxDim || a.cols > kSpeckleMaxDim) return hipErrorInvalidValue;
+    const uint64_t grid = speckle_grid(a, kSpeckleF32BandRows);
+    if (!grid || grid > 0x7fffffffull) return hipErrorInvalidValue;
+    const dim3 g((unsigned)grid), b(kSpeckleThreads);
+    switch (window) {
+    case 3: hipLaunchKernelGGL((k_speckle_f32<3>), g, b, 0, s, a); break;
+    case 5: hipLaunchKernelGGL((k_speckle_f32<5>), g, b, 0, s, a); break;
+    case 7: hipLaunchKernelGGL((k_speckle_f32<7>), g, b, 0, s, a); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+} // namespace sarpro

@@ -30,3 +30,8 @@ class SyntheticRgbMode(IntEnum):  # types.rs:177-182
     RgbRatio = 1
     SarUrban = 2
     Enhanced = 3
+
+
+class SpeckleFilter(IntEnum):  # sarpro_hip_speckle_filter: this library's own (the reference's roadmap names the filters, ships none)
+    Lee = 0
+    Kuan = 1
