@@ -57,6 +57,43 @@ def test_restart_cycle_wraps_and_scans_hold_stuffed_bytes():
     assert scan == jpegref.scan_bytes(pillow_file(img, 1))
 
 
+@pytest.mark.parametrize("nc", [1, 3])
+def test_crafted_raster_is_small_and_deterministic(nc):
+    img = jpegref.crafted_raster(nc)
+    assert img.dtype == np.uint8 and img.ndim == (2 if nc == 1 else 3) and img.size < 350_000   # samples: under 0.35 MP either way
+    n_mcus = img.shape[0] * img.shape[1] // 64
+    assert img.shape[0] % 8 == 0 and img.shape[1] % 8 == 0 and n_mcus > 1600 and n_mcus % 5   # an interval of 5 leaves a ragged segment
+    assert np.array_equal(img, jpegref.crafted_raster.__wrapped__(nc))
+
+
+@pytest.mark.parametrize("r", [None, 1, 5, 65535])
+@pytest.mark.parametrize("nc", [1, 3])
+def test_restatement_scan_of_the_crafted_raster_equals_pillow(nc, r):
+    """every (run, size) symbol of each table, single, double and triple ZRLs, blocks with and without EOB, every DC class and a
+    segment that ends in a stuffed FF: asserted on the raster first, then the restatement's scan against libjpeg-turbo's"""
+    img = jpegref.crafted_raster(nc)
+    jpegref.assert_full_coverage(jpegref.symbol_coverage(img, r), r)
+    ref = jpegref.scan_bytes(pillow_file(img, r))
+    assert jpegref.segments_ending_stuffed(ref) >= 1
+    assert len(jpegref.split_segments(ref)) == (-(-(img.shape[0] * img.shape[1] // 64) // r) if r else 1)
+    assert jpegref.encode_scan(img, r) == ref
+
+
+def test_symbol_coverage_counts_what_it_says():
+    """two hand-made coefficient blocks through the report's own counting (ac_events) and a raster whose report is known"""
+    q = np.zeros((2, 64), np.int64)
+    q[0, [1, 18, 63]] = [5, -1, 700]           # runs 0, 16, 44
+    q[1, [50]] = [-512]                        # run 49
+    b, run, size = jpegref.ac_events(q)
+    assert b.tolist() == [0, 0, 0, 1] and run.tolist() == [0, 16, 44, 49] and size.tolist() == [3, 1, 10, 10]
+    flat = np.repeat(np.repeat(np.array([[0, 255, 255, 130]], np.uint8), 8, 0), 8, 1)   # DCs -1024, 1016, 1016, 16
+    c = jpegref.symbol_coverage(flat, None)[0]
+    assert c == {"ac": set(), "runs": (0, 0, 0), "no_eob": 0, "eob": 4, "dc": {(11, -1), (11, 1), (0, 0), (10, -1)}}
+    assert jpegref.symbol_coverage(flat, 1)[0]["dc"] == {(11, -1), (10, 1), (5, 1)}
+    assert jpegref.symbol_coverage(flat, 2)[0]["dc"] == {(11, -1), (11, 1), (10, 1), (10, -1)}
+    assert set(jpegref.symbol_coverage(np.repeat(flat[..., None], 3, -1), 1)) == {0, 1}
+
+
 ANNEX_K_COUNTS = {(0, 0): [0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0], (0, 1): [0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0],
                   (1, 0): [0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d], (1, 1): [0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77]}
 
