@@ -480,7 +480,8 @@ int sarpro_hip_dualpol_synrgb_resized_stream_u16(sarpro_hip_ctx *ctx, sarpro_hip
  * The reference's default flow does not process full-resolution bands: SafeReader::open_with_options(.., target_size) has GDAL
  * resample each band while reading it (read_band_resampled), the long side going to target_size, and the raster core sees the
  * resulting few-MP non-integer f32 bands.  The filter is ResampleAlg::Average when the reduction is >= 4 (every GRD quicklook) and
- * Lanczos below (sentinel1.rs:1093-1102).  This section is that step for u16 bands and the Average filter, on the device.
+ * Lanczos below (sentinel1.rs:1093-1102).  This section is that step for u16 bands, on the device: the Average filter, and the
+ * Lanczos filter for per-axis ratios up to 5 (further down).
  *   shape   scale = min(ts / max(cols, rows), 1) in f64; out = max(round(n * scale), 1) per axis, round half away from zero.
  *   filter  the separable weighted box: per axis, destination sample j of m covers [j * r, min((j + 1) * r, n)) with r = n / m;
  *           a source sample weighs its overlap with that interval (1 for every interior sample).  Per destination pixel, for each
@@ -489,9 +490,10 @@ int sarpro_hip_dualpol_synrgb_resized_stream_u16(sarpro_hip_ctx *ctx, sarpro_hip
  *           w_sum_x * w_sum_y; one rounding to f32.  DESIGN.md 9b states it operation by operation; tests/readref.py is its
  *           restatement.  The results are a function of the definition alone (bit for bit, whatever the tiling or pitch).
  * Parity with GDAL's own Average is UNPINNED: GDAL is absent here and the reference does not lock its version; this is the weighted
- * box GDAL's average resampler documents, in its working precision for a Float32 buffer.  Lanczos on read (GDAL's kernel, reductions
- * below 4) is not built: such a request returns SARPRO_HIP_ERR_UNSUPPORTED. */
-#define SARPRO_HIP_ERR_UNSUPPORTED (-10) /* a documented combination that is not built (Lanczos on read) */
+ * box GDAL's average resampler documents, in its working precision for a Float32 buffer.  Lanczos on read (reductions below 4) is
+ * the section's second filter, below; the flows take it only on a context whose READ_LANCZOS attribute is on and return
+ * SARPRO_HIP_ERR_UNSUPPORTED otherwise. */
+#define SARPRO_HIP_ERR_UNSUPPORTED (-10) /* a documented combination that is not built or not switched on (Lanczos on read) */
 typedef enum {
     SARPRO_READ_DEFAULT = -1, /* the rule of sentinel1.rs:1093-1102 */
     SARPRO_READ_AVERAGE = 0,
@@ -522,7 +524,13 @@ int sarpro_hip_read_average_u16(sarpro_hip_ctx *ctx, const uint16_t *in, size_t 
  * only the pad remains, as in the reference.  d_rgb_out: final_rows * final_cols * 3 bytes, where (final_cols, final_rows) =
  * sarpro_hip_resize_output_dims(out_cols, out_rows, target_size, pad).  alg: SARPRO_READ_DEFAULT follows the rule; an explicit
  * SARPRO_READ_AVERAGE is honoured at any reduction >= 1; Lanczos, chosen by the rule or requested, returns
- * SARPRO_HIP_ERR_UNSUPPORTED with a message naming the reduction (nothing is written). */
+ * SARPRO_HIP_ERR_UNSUPPORTED with a message naming the reduction (nothing is written) -- UNLESS the context attribute READ_LANCZOS
+ * is on (sarpro_hip_ctx_set_attr(ctx, "READ_LANCZOS", 1), or SARPRO_HIP_READ_LANCZOS in the environment when the context is created).
+ * Then, in all four flows of this section: SARPRO_READ_DEFAULT follows the rule to either filter (every shape the rule sends to
+ * Lanczos has per-axis ratios <= 5); an explicit SARPRO_READ_LANCZOS is honoured wherever both per-axis ratios are <= 5 and returns
+ * SARPRO_HIP_ERR_UNSUPPORTED with a message naming the ratios beyond; SARPRO_READ_AVERAGE is unchanged.  The filtered f32 bands go to
+ * sarpro_hip_dualpol_synrgb_resized_f32_dev either way (kernel time: read_lanczos in place of read_average).  The switch exists only
+ * because the suite pins the refusal on a default context; making the rule's choice the default is a one-line follow-up. */
 int sarpro_hip_dualpol_synrgb_read_u16_dev(sarpro_hip_ctx *ctx, const uint16_t *d_band1, const uint16_t *d_band2, size_t rows, size_t cols,
                                            size_t in_pitch, int alg, int strategy, int mode, unsigned flags, size_t target_size, int pad,
                                            uint8_t *d_rgb_out, sarpro_hip_resize_meta *meta);
@@ -540,6 +548,31 @@ int sarpro_hip_dualpol_synrgb_read_stream_u16_jpeg(sarpro_hip_ctx *ctx, sarpro_h
                                                    size_t cols, int alg, int strategy, int mode, unsigned flags, size_t target_size, int pad,
                                                    uint8_t *jpeg_out, size_t jpeg_capacity, size_t *jpeg_bytes_out, unsigned restart_mcus,
                                                    sarpro_hip_resize_meta *meta);
+
+/* ---- the Lanczos filter on read (restated in tests/readlanczosref.py).  Parity with GDAL's own Lanczos is UNPINNED:
+ * GDAL is absent here and the reference does not lock its version; this is the a = 3 Lanczos kernel with its support scaled by the
+ * reduction, as GDAL's resampler documents it, in f64 with one rounding to f32.
+ *   per axis   n source samples -> m destination samples, 1 <= m <= n, n / m <= 5.  m == n: the identity (one tap, weight 1.0).
+ *              m < n, all in f64: r = n / m; s = 3.0 * r; x = (j + 0.5) * r; first = max(0, (int)floor(x - s + 0.5));
+ *              end = min(n, (int)floor(x + s + 0.5)); taps c = first .. end - 1 (at most 30); t = ((c + 0.5) - x) / r;
+ *              raw = 1.0 if t == 0, 0.0 if |t| >= 3, else with pt = M_PI * t: (3.0 * sin(pt) * sin(pt / 3.0)) / (pt * pt) (glibc sin);
+ *              tot = the raw weights added in ascending c from 0.0; w[c] = raw[c] / tot.  Taps clipped at the raster's edge are dropped
+ *              before normalising.
+ *   per pixel  H[y][j] = sum_c w_x[j][c] * (double)v[y][c] in ascending c from 0.0; out[i][j] = (float) sum_y w_y[i][y] * H[y][j] in
+ *              ascending y from 0.0; every product and every sum rounded on its own (nothing fused), one round-to-nearest-even to
+ *              f32.  NO CLAMP: a result may be negative or above 65535 (the kernel's lobes are signed); downstream such pixels count
+ *              as invalid exactly as negative input of the f32 chain does.  H depends on (y, j) alone: the results are a function of
+ *              the definition (bit for bit, whatever the tiling, pitch or load width).
+ * One axis' tables (no GPU): first[n_dst], count[n_dst] and weights[n_dst * 32] -- 32 slots per destination sample, unused slots 0.0.
+ * INVALID_ARG outside 1 <= n_dst <= n_src <= 2^30, when n_src / n_dst > 5, on a null pointer. */
+int sarpro_hip_host_read_lanczos_axis(size_t n_src, size_t n_dst, uint32_t first[], uint32_t count[], double weights[]);
+/* The Lanczos filter with the rules of sarpro_hip_read_average_u16_dev (shapes, pitches, load paths, stream order).  A per-axis ratio
+ * above 5: SARPRO_HIP_ERR_UNSUPPORTED with a message naming the ratios; nothing is written.  Kernel time: read_lanczos. */
+int sarpro_hip_read_lanczos_u16_dev(sarpro_hip_ctx *ctx, const uint16_t *d_in, size_t rows, size_t cols, size_t in_pitch, size_t out_rows,
+                                    size_t out_cols, float *d_out_f32, size_t out_pitch);
+/* The same with host pointers (compact rasters). */
+int sarpro_hip_read_lanczos_u16(sarpro_hip_ctx *ctx, const uint16_t *in, size_t rows, size_t cols, size_t out_rows, size_t out_cols,
+                                float *out_f32);
 
 /* ================= speckle filtering: Lee and Kuan over u16 and f32 bands =================
  * The next per-pixel step SAR users expect, Phase 4 of the reference's roadmap (Lee, Kuan, Frost, Refined Lee; windows of 3-7 px;

@@ -443,10 +443,24 @@ impl RasterCore {
             .map_err(|_| HipError { code: sys::SARPRO_HIP_ERR_SHAPE_MISMATCH, message: "output shape".into() })
     }
 
+    /// `GdalSarReader::read_band_resampled(1, out_cols, out_rows, Some(ResampleAlg::Lanczos))` for a u16 measurement band held in
+    /// memory: the a = 3 Lanczos kernel with its support scaled by the reduction, on the device, for per-axis ratios up to 5
+    /// (`SARPRO_HIP_ERR_UNSUPPORTED` beyond).  Not clamped: results may be negative or above 65535.  Parity with GDAL's own filter is
+    /// unpinned.
+    pub fn try_read_band_resampled_lanczos(&self, band: &Array2<u16>, out_cols: usize, out_rows: usize) -> Result<Array2<f32>> {
+        let (rows, cols) = band.dim();
+        let b = band.as_standard_layout();
+        let mut out = vec![0f32; out_cols * out_rows];
+        self.chk(unsafe { sys::sarpro_hip_read_lanczos_u16(self.ctx, b.as_ptr(), rows, cols, out_rows, out_cols, out.as_mut_ptr()) })?;
+        Array2::from_shape_vec((out_rows, out_cols), out)
+            .map_err(|_| HipError { code: sys::SARPRO_HIP_ERR_SHAPE_MISMATCH, message: "output shape".into() })
+    }
+
     /// The default flow from the raw bands (sentinel1.rs:1103-1105 per band, then api/mod.rs:404-437 when `plain_pipeline`, save.rs:317-367
-    /// otherwise): both u16 bands averaged on read to the long side `target_size`, per-band u8, pad, synRGB.  `average = None` follows
-    /// the reference's rule (Lanczos below a reduction of 4 is not built: `SARPRO_HIP_ERR_UNSUPPORTED`), `Some(true)` averages at
-    /// any reduction.
+    /// otherwise): both u16 bands filtered on read to the long side `target_size`, per-band u8, pad, synRGB.  `average = None` follows
+    /// the reference's rule, `Some(true)` averages at any reduction, `Some(false)` asks for Lanczos (per-axis ratios up to 5).  The
+    /// Lanczos filter enters this flow only after `set_attr("READ_LANCZOS", 1)`; on a context without that attribute a request the rule
+    /// or the caller sends to Lanczos returns `SARPRO_HIP_ERR_UNSUPPORTED`, as before the filter was built.
     pub fn try_render_multiband_image_read_u16(&self, band1: &Array2<u16>, band2: &Array2<u16>, target_size: usize, pad: bool,
         autoscale: AutoscaleStrategy, syn_mode: SyntheticRgbMode, plain_pipeline: bool, average: Option<bool>) -> Result<ProcessedImage> {
         if band1.dim() != band2.dim() {

@@ -117,6 +117,7 @@ SYMBOLS = [
     "sarpro_hip_read_output_dims", "sarpro_hip_host_read_average_axis", "sarpro_hip_read_average_u16_dev", "sarpro_hip_read_average_u16",
     "sarpro_hip_dualpol_synrgb_read_u16_dev", "sarpro_hip_dualpol_synrgb_read_u16", "sarpro_hip_dualpol_synrgb_read_stream_u16",
     "sarpro_hip_dualpol_synrgb_read_stream_u16_jpeg",
+    "sarpro_hip_host_read_lanczos_axis", "sarpro_hip_read_lanczos_u16_dev", "sarpro_hip_read_lanczos_u16",
     "sarpro_hip_speckle_u16_dev", "sarpro_hip_speckle_f32_dev", "sarpro_hip_speckle_u16", "sarpro_hip_speckle_f32",
     "sarpro_hip_dualpol_synrgb_speckle_u16_dev", "sarpro_hip_dualpol_synrgb_speckle_u16",
 ]
@@ -298,6 +299,9 @@ _proto("sarpro_hip_dualpol_synrgb_read_u16_dev", _i, _vp, _vp, _vp, _sz, _sz, _s
 _proto("sarpro_hip_dualpol_synrgb_read_u16", _i, _vp, _vp, _vp, _sz, _sz, _i, _i, _i, _u, _sz, _i, _vp, _M)
 _proto("sarpro_hip_dualpol_synrgb_read_stream_u16", _i, _vp, _vp, _vp, _sz, _sz, _i, _i, _i, _u, _sz, _i, _vp, _M)
 _proto("sarpro_hip_dualpol_synrgb_read_stream_u16_jpeg", _i, _vp, _vp, _vp, _sz, _sz, _i, _i, _i, _u, _sz, _i, _vp, _sz, C.POINTER(_sz), _u, _M)
+_proto("sarpro_hip_host_read_lanczos_axis", _i, _sz, _sz, _vp, _vp, _vp)
+_proto("sarpro_hip_read_lanczos_u16_dev", _i, _vp, _vp, _sz, _sz, _sz, _sz, _sz, _vp, _sz)
+_proto("sarpro_hip_read_lanczos_u16", _i, _vp, _vp, _sz, _sz, _sz, _sz, _vp)
 _d = C.c_double
 for _n in ("sarpro_hip_speckle_u16_dev", "sarpro_hip_speckle_f32_dev"):
     _proto(_n, _i, _vp, _vp, _sz, _sz, _sz, _i, _i, _d, _vp, _sz)

@@ -445,6 +445,19 @@ class Context:
         """read_average with the u16 band (in_pitch elements per row) and the f32 raster (out_pitch elements per row) in device memory."""
         self._chk(lib.sarpro_hip_read_average_u16_dev(self._h, _vp(d_in), rows, cols, in_pitch, out_rows, out_cols, _vp(d_out), out_pitch))
 
+    def read_lanczos(self, band: np.ndarray, out_rows: int, out_cols: int) -> np.ndarray:
+        """read_band_resampled with ResampleAlg::Lanczos for a u16 band (DESIGN.md 9d; per-axis ratios up to 5):
+        (rows, cols) uint16 -> (out_rows, out_cols) float32, not clamped."""
+        b = np.ascontiguousarray(band, np.uint16)
+        rows, cols = b.shape
+        out = np.empty((out_rows, out_cols), np.float32)
+        self._chk(lib.sarpro_hip_read_lanczos_u16(self._h, _vp(b), rows, cols, out_rows, out_cols, _vp(out)))
+        return out
+
+    def dev_read_lanczos(self, d_in: int, rows: int, cols: int, in_pitch: int, out_rows: int, out_cols: int, d_out: int, out_pitch: int):
+        """read_lanczos with the u16 band (in_pitch elements per row) and the f32 raster (out_pitch elements per row) in device memory."""
+        self._chk(lib.sarpro_hip_read_lanczos_u16_dev(self._h, _vp(d_in), rows, cols, in_pitch, out_rows, out_cols, _vp(d_out), out_pitch))
+
     @staticmethod
     def _read_final_dims(cols: int, rows: int, target_size: int, pad: bool):
         oc, orows, _ = read_output_dims(cols, rows, target_size)
@@ -1077,6 +1090,16 @@ def host_read_average_axis(n_src: int, n_dst: int):
     if rc != _lib.OK:
         raise SarproHipError(rc, "host_read_average_axis: 1 <= n_dst <= n_src <= 2^30")
     return first, count, wf, wl, ws
+
+
+def host_read_lanczos_axis(n_src: int, n_dst: int):
+    """One axis of the Lanczos filter (no GPU) -> (first, count, weights): uint32 [n_dst], uint32 [n_dst], f64 [n_dst, 32] (unused slots 0)."""
+    n = max(int(n_dst), 0)
+    first, count, w = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros((n, 32), np.float64)
+    rc = lib.sarpro_hip_host_read_lanczos_axis(n_src, n_dst, _vp(first), _vp(count), _vp(w))
+    if rc != _lib.OK:
+        raise SarproHipError(rc, "host_read_lanczos_axis: 1 <= n_dst <= n_src <= 2^30, n_src / n_dst <= 5")
+    return first, count, w
 
 
 def batch_dualpol_synrgb_resized(devices, scenes, strategy, target_size, pad, mode=SyntheticRgbMode.Default,

@@ -176,7 +176,8 @@ struct BandWorker {
     X(STRIP_ALIGN) X(PIECE_ALIGN) X(CHUNK_ROWS) X(RGB_ITEM_ROWS) X(SAMPLE_ITEM_ROWS) \
     X(NO_MAILBOX) X(NO_STEP_ESTIMATE) X(F32_ZONES) X(F32_ZONES_DEBUG) X(F32_DIRECT) X(F32_DIRECT_QCAP) X(F32_LEVEL_GENERAL) \
     X(F32_LEVEL_TABLE) X(F32_LEVEL_QCAP) X(F32_HOST_CDFS) X(F32_NO_VEC8) X(NO_BAND_TWIN) X(RESIZE_GENERIC) X(NO_RESIZE_LUT) \
-    X(NO_U16_CF) X(U16_ITEM_ROWS) X(PIPE_LANES) X(PIPE_ORDER) X(RGB_GRID) X(PIECE_GRID) X(COMM_RECORD) X(COMM_REPLAY) X(NO_SPEC_RESCALE) X(RGB_TAIL_ROWS) X(RGB_TAIL_ITEM_ROWS)
+    X(NO_U16_CF) X(U16_ITEM_ROWS) X(PIPE_LANES) X(PIPE_ORDER) X(RGB_GRID) X(PIECE_GRID) X(COMM_RECORD) X(COMM_REPLAY) X(NO_SPEC_RESCALE) X(RGB_TAIL_ROWS) X(RGB_TAIL_ITEM_ROWS) \
+    X(READ_LANCZOS)
 namespace sarpro {
 enum Attr : int {
 #define X(n) A_##n,
@@ -235,6 +236,12 @@ struct sarpro_hip_ctx {
     sarpro::DevBuf read_tab, read_src[2], read_band[2];
     sarpro::PinnedBuf read_host;
     size_t read_key[4] = {0, 0, 0, 0};
+    // ... and the Lanczos filter's tables (the weights of both axes, then first | count of both axes), cached the same way,
+    // with the widest column window of the cached shape
+    sarpro::DevBuf lanczos_tab;
+    sarpro::PinnedBuf lanczos_host;
+    size_t lanczos_key[4] = {0, 0, 0, 0};
+    uint32_t lanczos_col_taps = 0;
     sarpro::DevBuf speckle_band[2];              // speckle filtering (speckle_path.cpp): the filtered f32 rasters of the host forms and the flows
     sarpro::DevBuf chain_consts;                 // device-resident chain: dB table | suppressed lut_r/g per floor | blue pairs
     sarpro::DevBuf chain_scratch;               // statistics step: per-slice partials | 4096 bins per band

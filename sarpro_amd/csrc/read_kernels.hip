@@ -1,4 +1,5 @@
-// read_kernels.hip -- downsample on read: the area average of u16 bands to f32 (io/sentinel1.rs:1074-1108 -> io/gdal.rs:145-177 with
+// read_kernels.hip -- downsample on read: the Lanczos filter of u16 bands to f32 (the second half of this file) and the
+// area average of u16 bands to f32 (io/sentinel1.rs:1074-1108 -> io/gdal.rs:145-177 with
 // ResampleAlg::Average), DESIGN.md 9b.  A destination pixel is the separable weighted box over its source window: per source row the
 // EXACT integer sum of the window's interior columns plus the two edge samples times their f64 weights, the rows of the window
 // accumulated top to bottom in f64 with the row weights, one correctly rounded division by the window's weight, one rounding to f32.
@@ -173,6 +174,144 @@ hipError_t launch_read_average_u16(const ReadArgs &a, bool vec, hipStream_t s) {
     else if (vec) hipLaunchKernelGGL((k_read_average_u16<true, false>), dim3((unsigned)grid), dim3(kReadThreads), 0, s, a);
     else if (one) hipLaunchKernelGGL((k_read_average_u16<false, true>), dim3((unsigned)grid), dim3(kReadThreads), 0, s, a);
     else hipLaunchKernelGGL((k_read_average_u16<false, false>), dim3((unsigned)grid), dim3(kReadThreads), 0, s, a);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The Lanczos filter (a = 3) of the same step, DESIGN.md 9d.  out[i][j] = (float) sum_y w_y[i][y] * H[y][j] with H[y][j] = sum_c
+// w_x[j][c] * (double)v[y][c]: both sums in ascending order from 0.0, every product and sum rounded on its own, one rounding to f32.
+// H depends on (y, j) alone, so the result does not depend on the tiling.  ONE pass, H never leaves the registers: a workgroup owns a
+// strip of <= 256 destination columns (one lane each) x a band of <= 64 destination rows and walks the band's source rows top to
+// bottom through the double-buffered LDS slabs of the Average pass (one slab per row: a strip spans <= 1318 source columns at the
+// largest ratio, 5).  Per source row a lane forms H from LDS with its own NT column weights (registers; slots past the window weigh 0.0
+// and add +0.0: bit-neutral) and adds w_y * H into the open accumulators: destination row i accumulates in ring entry (i - i0) % 8
+// (window i is complete before window i + 8 opens: the host checks the tables), the ring and its bookkeeping statically indexed --
+// the loop over the entries is unrolled and every branch in it is workgroup-uniform.  The row weights of the band sit in LDS.
+namespace {
+constexpr uint32_t kLzVecPerUnit = kLanczosChunk / 8;                                  // 16-byte vectors of a slab
+constexpr uint32_t kLzLoadsPerLane = kLanczosUnits * kLzVecPerUnit / kReadThreads;     // 3
+static_assert(kLanczosUnits * kLzVecPerUnit % kReadThreads == 0, "a stage is a whole number of vectors per lane");
+static_assert(kLanczosChunk % 8 == 0 && kLanczosChunk >= kReadThreads * 5 + 30 + 7 + kLanczosTaps, "a strip's span at a ratio of 5, plus the slack of the unused tap slots");
+} // namespace
+
+template <bool VEC, uint32_t NT>
+__global__ __launch_bounds__(kReadThreads) void k_read_lanczos_u16(LanczosArgs a) {
+    __shared__ uint4 s_slab[2][kLanczosUnits][kLzVecPerUnit];
+    __shared__ double s_wrow[kLanczosMaxBandRows * kLanczosTaps];
+    __shared__ uint32_t s_rfirst[kLanczosMaxBandRows], s_rend[kLanczosMaxBandRows];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t nstrips = (a.out_cols + kReadThreads - 1) / kReadThreads;
+    const uint32_t nrb = (a.out_rows + a.band_rows - 1) / a.band_rows;
+    uint32_t t = blockIdx.x; // strips fastest: neighbouring workgroups read neighbouring spans of the same source rows
+    const uint32_t strip = t % nstrips;
+    t /= nstrips;
+    const uint32_t rb = t % nrb, band = t / nrb;
+    const uint16_t *src = band ? a.src[1] : a.src[0];
+    float *dst = band ? a.dst[1] : a.dst[0];
+    const uint32_t j0 = strip * kReadThreads, j1 = min(j0 + kReadThreads, a.out_cols);
+    const uint32_t i0 = rb * a.band_rows, i1 = min(i0 + a.band_rows, a.out_rows), nb = i1 - i0;
+    for (uint32_t e = tid; e < nb * kLanczosTaps; e += kReadThreads) s_wrow[e] = a.row_w[(size_t)i0 * kLanczosTaps + e];
+    if (tid < nb) {
+        const uint32_t f = a.row_first[i0 + tid];
+        s_rfirst[tid] = f; s_rend[tid] = f + a.row_count[i0 + tid];
+    }
+    // the tile's source rectangle: columns [cs, ce) (cs on a vector boundary), rows [ys, ye)
+    const uint32_t cs = a.col_first[j0] & ~7u, ce = a.col_first[j1 - 1] + a.col_count[j1 - 1];
+    const uint32_t ys = a.row_first[i0], ye = a.row_first[i1 - 1] + a.row_count[i1 - 1];
+    const uint32_t nunits = ye - ys; // unit u = the slab of source row ys + u
+    const uint32_t nstages = (nunits + kLanczosUnits - 1) / kLanczosUnits;
+    // the lane's destination column: where its window starts in the slab, its weights (idle lanes: weights 0.0 at the slab's start)
+    const bool active = tid < j1 - j0;
+    uint32_t off = 0;
+    double w[NT];
+#pragma unroll
+    for (uint32_t k = 0; k < NT; ++k) w[k] = 0.0;
+    if (active) {
+        off = a.col_first[j0 + tid] - cs;
+        const double *p = a.col_w + (size_t)(j0 + tid) * kLanczosTaps;
+#pragma unroll
+        for (uint32_t k = 0; k < NT; ++k) w[k] = p[k];
+    }
+    // the lane's vectors of a stage: vector v = tid + q * 256 is vector v % kLzVecPerUnit of the stage's unit v / kLzVecPerUnit
+    uint32_t qy[kLzLoadsPerLane];
+#pragma unroll
+    for (uint32_t q = 0; q < kLzLoadsPerLane; ++q) qy[q] = ys + (tid + q * kReadThreads) / kLzVecPerUnit;
+    uint4 regs[kLzLoadsPerLane];
+    auto load_stage = [&]() {
+#pragma unroll
+        for (uint32_t q = 0; q < kLzLoadsPerLane; ++q) {
+            const uint32_t col = cs + (tid + q * kReadThreads) % kLzVecPerUnit * 8;
+            regs[q] = make_uint4(0u, 0u, 0u, 0u);
+            if (qy[q] < ye && col < ce) regs[q] = read_fetch8<VEC>(src + (size_t)qy[q] * a.in_pitch, col, a.cols);
+            qy[q] += kLanczosUnits;
+        }
+    };
+    auto write_stage = [&](uint32_t half) {
+#pragma unroll
+        for (uint32_t q = 0; q < kLzLoadsPerLane; ++q) {
+            const uint32_t v = tid + q * kReadThreads;
+            s_slab[half][v / kLzVecPerUnit][v % kLzVecPerUnit] = regs[q];
+        }
+    };
+    load_stage();
+    write_stage(0);
+    __syncthreads();
+    // the ring: entry e holds destination row i0 + li[e] (li[e] % 8 == e) with its window [rf[e], re[e]) of source rows (uniform; no
+    // row left: an empty window past every row) and, per lane, the running sum
+    double acc[kLanczosRing];
+    uint32_t li[kLanczosRing], rf[kLanczosRing], re[kLanczosRing];
+#pragma unroll
+    for (uint32_t e = 0; e < kLanczosRing; ++e) {
+        acc[e] = 0.0; li[e] = e; rf[e] = 0xffffffffu; re[e] = 0xffffffffu;
+        if (e < nb) { rf[e] = __builtin_amdgcn_readfirstlane(s_rfirst[e]); re[e] = __builtin_amdgcn_readfirstlane(s_rend[e]); }
+    }
+    uint32_t y = ys;
+    for (uint32_t s = 0; s < nstages; ++s) {
+        const bool more = s + 1 < nstages;
+        if (more) load_stage();
+        const uint32_t nu = min(kLanczosUnits, nunits - s * kLanczosUnits);
+        for (uint32_t ul = 0; ul < nu; ++ul, ++y) {
+            const uint16_t *slab = reinterpret_cast<const uint16_t *>(&s_slab[s & 1][ul][0]) + off;
+#ifndef SARPRO_LANCZOS_ABLATE_TAPS // (timing variant, tools/build_variant.sh: the pass without the lanes' tap reads and f64 products -- wrong results)
+            double H = 0.0;
+#pragma unroll
+            for (uint32_t k = 0; k < NT; ++k) H = H + w[k] * (double)slab[k];
+#else
+            const double H = w[0] * (double)slab[0];
+#endif
+#pragma unroll
+            for (uint32_t e = 0; e < kLanczosRing; ++e) {
+                if (y >= rf[e] && y < re[e]) {
+                    acc[e] = acc[e] + s_wrow[li[e] * kLanczosTaps + (y - rf[e])] * H;
+                    if (y + 1 == re[e]) { // the window is complete: the one rounding to f32; the entry takes its next destination row
+                        if (active) dst[(size_t)(i0 + li[e]) * a.out_pitch + j0 + tid] = (float)acc[e];
+                        acc[e] = 0.0;
+                        li[e] += kLanczosRing;
+                        rf[e] = 0xffffffffu; re[e] = 0xffffffffu;
+                        if (li[e] < nb) { rf[e] = __builtin_amdgcn_readfirstlane(s_rfirst[li[e]]); re[e] = __builtin_amdgcn_readfirstlane(s_rend[li[e]]); }
+                    }
+                }
+            }
+        }
+        if (more) write_stage((s + 1) & 1);
+        __syncthreads();
+    }
+}
+
+template <bool VEC>
+static void launch_lanczos_class(const LanczosArgs &a, unsigned grid, hipStream_t s) {
+    if (a.col_taps <= 8) hipLaunchKernelGGL((k_read_lanczos_u16<VEC, 8>), dim3(grid), dim3(kReadThreads), 0, s, a);
+    else if (a.col_taps <= 16) hipLaunchKernelGGL((k_read_lanczos_u16<VEC, 16>), dim3(grid), dim3(kReadThreads), 0, s, a);
+    else if (a.col_taps <= 24) hipLaunchKernelGGL((k_read_lanczos_u16<VEC, 24>), dim3(grid), dim3(kReadThreads), 0, s, a);
+    else hipLaunchKernelGGL((k_read_lanczos_u16<VEC, 32>), dim3(grid), dim3(kReadThreads), 0, s, a);
+}
+
+hipError_t launch_read_lanczos_u16(const LanczosArgs &a, bool vec, hipStream_t s) {
+    const uint64_t nstrips = (a.out_cols + kReadThreads - 1) / kReadThreads, nrb = a.band_rows ? (a.out_rows + a.band_rows - 1) / a.band_rows : 0;
+    const uint64_t grid = nstrips * nrb * a.nbands;
+    if (!grid || grid > 0x7fffffffull || a.band_rows > kLanczosMaxBandRows || !a.col_taps || a.col_taps > kLanczosTaps) return hipErrorInvalidValue;
+    if (vec) launch_lanczos_class<true>(a, (unsigned)grid, s);
+    else launch_lanczos_class<false>(a, (unsigned)grid, s);
     return hipGetLastError();
 }
 
