@@ -602,8 +602,10 @@ int sarpro_hip_read_lanczos_u16(sarpro_hip_ctx *ctx, const uint16_t *in, size_t 
  *   properties  a constant raster comes back unchanged (65535 gives exactly 65535.0); out lies between m and v; a valid centre stays
  *               valid; with very few looks w is 0 everywhere and the result is the boxcar mean of the valid samples; with very many
  *               looks the result approaches the input.
- * Not built: Frost, Refined Lee, windows above 7, a u16 -> u16 form, filtering inside the batch / stream / _jpeg / stripe flows. */
-typedef enum { SARPRO_SPECKLE_LEE = 0, SARPRO_SPECKLE_KUAN = 1 } sarpro_hip_speckle_filter;
+ * Frost and Refined Lee over u16 bands: the _ext entry points further below; the calls of this section keep refusing them.
+ * Not built: windows above 7, a u16 -> u16 form, f32 forms of Frost and Refined Lee, filtering inside the batch / stream / _jpeg /
+ * stripe flows. */
+typedef enum { SARPRO_SPECKLE_LEE = 0, SARPRO_SPECKLE_KUAN = 1, SARPRO_SPECKLE_FROST = 2, SARPRO_SPECKLE_REFINED_LEE = 3 } sarpro_hip_speckle_filter;
 /* rows x cols samples (in_pitch elements per row) -> rows x cols f32 (out_pitch elements per row; the padding is not written), both in
  * device memory; any shape >= 1 x 1, rasters smaller than the window included.  Stream-ordered on the context's stream and synchronous
  * like the other _dev calls (on a SARPRO_HIP_CTX_ASYNC_DEV context it returns once enqueued).  u16: 16-byte loads when in_pitch % 8 ==
@@ -631,6 +633,64 @@ int sarpro_hip_dualpol_synrgb_speckle_u16_dev(sarpro_hip_ctx *ctx, const uint16_
 int sarpro_hip_dualpol_synrgb_speckle_u16(sarpro_hip_ctx *ctx, const uint16_t *band1, const uint16_t *band2, size_t rows, size_t cols,
                                           int filter, int window, double looks, int strategy, int mode, unsigned flags, size_t target_size,
                                           int pad, uint8_t *rgb_out, sarpro_hip_resize_meta *meta);
+
+/* ================= speckle filtering: Frost and Refined Lee over u16 bands =================
+ * The other two filters of the roadmap's Phase 4.  As above THE DEFINITIONS ARE THIS PROJECT'S OWN, fixed here operation by operation;
+ * the result is a function of them alone, bit for bit, whatever the tiling, the pitch or the load width; the kernels are tested by f32
+ * bit pattern against the numpy restatement tests/speckleextref.py.  u16 bands only.
+ *   common      as above: a sample is valid iff v >= 1; the window is clipped to the raster, no reflection; only valid samples count;
+ *               an invalid centre gives 0.0f; f64 throughout, nothing contracted, one round-to-nearest-even conversion to f32.
+ *   EXP(x)      for x <= 0, the library's own exponential (no libm is trusted).  LOG2E = 0x1.71547652b82fep+0, LN2_HI =
+ *               0x1.62e42fee00000p-1, LN2_LO = 0x1.a39ef35793c76p-33 (fdlibm's split of ln 2), c_i = 1.0 / (double)(i!) for i = 0..13,
+ *               each one correctly rounded division (every i! is exact in f64).
+ *                 1. x < -708.0 (-inf included): +0.0.
+ *                 2. kf = rint(x * LOG2E), ties to even.
+ *                 3. r = (x - kf * LN2_HI) - kf * LN2_LO.
+ *                 4. p = c_13; for i = 12 down to 0: p = p * r + c_i, one multiplication then one addition.
+ *                 5. ldexp(p, (int)kf), exact since kf >= -1022.
+ *               EXP(0) = 1.0, results lie in (0, 1], within 1 ulp of a correctly rounded exp where measured.
+ *   Frost       window k in {3, 5, 7}, h = k / 2, damping: a finite f64 > 0; looks is ignored.  Valid centre v, n >= 1 valid samples:
+ *                 S1, S2, A = S1 * S1, D = n * S2 - A exact integers as above (A >= 1);  a = damping * ((double)D / (double)A).
+ *                 The window's offsets fall into classes by r2 = dy^2 + dx^2: {0,1,2}, {0,1,2,4,5,8}, {0,1,2,4,5,8,9,10,13,18} for
+ *                 k = 3, 5, 7.  T_c = the exact integer sum of the class's valid samples, N_c their number;
+ *                 dist_c = sqrt((double)r2), IEEE-correct;  w_0 = 1.0, w_c = EXP(-(a * dist_c)) for c > 0.
+ *                 From num = den = 0.0, over the classes in ascending r2: num = num + w_c * (double)T_c; den = den + w_c * (double)N_c
+ *                 (an empty class adds +0.0).  out = (float)(num / den).
+ *               D / A is the squared coefficient of variation of the window, so the weight is the classical exp(-K * Ci^2 * |t|).
+ *               Every output is finite (a may overflow to +inf: EXP gives 0) and lies between the smallest and the largest valid
+ *               sample of the window; a constant raster comes back unchanged; damping >= 1e6 returns the input.
+ *   Refined Lee window 7, looks: a finite f64 > 0, cu2 = 1.0 / looks; damping is ignored.
+ *               Fallback: if the 7 x 7 window is not wholly inside the raster, or any of its 49 samples is invalid, the output is
+ *               exactly that of Lee with window 7 above, bit for bit.
+ *               Directed (all 49 samples present and valid): B_ij, i, j in {0,1,2}, = the integer sum of the 3 x 3 block whose
+ *               top-left offset is (dy, dx) = (-3 + 2i, -3 + 2j).  Integer gradients
+ *                 g0 = |(B02+B12+B22) - (B00+B10+B20)|   g1 = |(B01+B02+B12) - (B10+B20+B21)|
+ *                 g2 = |(B00+B01+B02) - (B20+B21+B22)|   g3 = |(B00+B01+B10) - (B12+B21+B22)|
+ *               d = the index of the largest, the lowest index on a tie.  Each d has a pair (P, Q) and the half-window each selects:
+ *                 d0: P = B12 -> E (dx >= 0),   Q = B10 -> W (dx <= 0)      d1: P = B02 -> NE (dx >= dy),     Q = B20 -> SW (dx <= dy)
+ *                 d2: P = B01 -> N (dy <= 0),   Q = B21 -> S (dy >= 0)      d3: P = B00 -> NW (dx + dy <= 0), Q = B22 -> SE (dx + dy >= 0)
+ *               P's half-window if |P - B11| <= |Q - B11|, else Q's: 28 samples, the centre among them.  Over it, with n = 28: S1, S2,
+ *               A = S1 * S1, D = 28 * S2 - A exact integers, m = S1 / 28.0;  !(D > 0): out = (float)m;  else q = (cu2 * A) / D,
+ *               w = 1.0 - q, w = 0 if !(w > 0), out = (float)(m + w * ((double)v - m)).
+ * The _ext calls accept all four filters.  With SARPRO_SPECKLE_LEE or SARPRO_SPECKLE_KUAN they give exactly what the calls above give
+ * (the same kernel, the same bits; damping is ignored).  Stream order, synchrony, SARPRO_HIP_CTX_ASYNC_DEV, pitches, alignment and the
+ * choice between 16-byte and element loads are those of sarpro_hip_speckle_u16_dev; the output's padding is not written; any shape
+ * >= 1 x 1.  SARPRO_HIP_ERR_INVALID_ARG with a message, nothing written: everything the calls above reject, a filter outside 0..3,
+ * Frost with a window not in {3, 5, 7} or a damping that is not finite or <= 0, Refined Lee with a window other than 7 or looks not
+ * finite or <= 0.  Kernel times: speckle_frost_u16, speckle_rlee_u16 (Lee, Kuan: speckle_u16). */
+int sarpro_hip_speckle_ext_u16_dev(sarpro_hip_ctx *ctx, const uint16_t *d_in, size_t rows, size_t cols, size_t in_pitch, int filter, int window,
+                                   double looks, double damping, float *d_out_f32, size_t out_pitch);
+int sarpro_hip_speckle_ext_u16(sarpro_hip_ctx *ctx, const uint16_t *in, size_t rows, size_t cols, int filter, int window, double looks,
+                               double damping, float *out_f32);
+/* The flows of sarpro_hip_dualpol_synrgb_speckle_u16(_dev) with any of the four filters: they differ in the filter step alone. */
+int sarpro_hip_dualpol_synrgb_speckle_ext_u16_dev(sarpro_hip_ctx *ctx, const uint16_t *d_band1, const uint16_t *d_band2, size_t rows, size_t cols,
+                                                  size_t in_pitch, int filter, int window, double looks, double damping, int strategy, int mode,
+                                                  unsigned flags, size_t target_size, int pad, uint8_t *d_rgb_out, sarpro_hip_resize_meta *meta);
+int sarpro_hip_dualpol_synrgb_speckle_ext_u16(sarpro_hip_ctx *ctx, const uint16_t *band1, const uint16_t *band2, size_t rows, size_t cols,
+                                              int filter, int window, double looks, double damping, int strategy, int mode, unsigned flags,
+                                              size_t target_size, int pad, uint8_t *rgb_out, sarpro_hip_resize_meta *meta);
+/* EXP of the definition above on the host (no GPU): the same source sequence as the kernels'.  NaN for a NaN or x > 0. */
+double sarpro_hip_host_speckle_exp(double x);
 
 /* ---- file shims for the two callbacks: uncompressed strip TIFF / BigTIFF (what Sentinel-1 GRD measurement rasters
  * are; io/gdal.rs:107-141 and io/writers/tiff.rs:6-78 go through GDAL).  Baseline TIFF 6.0 + BigTIFF, II or MM,

@@ -54,10 +54,11 @@ pub mod types {
     #[derive(Copy, Clone, PartialEq, Eq, PartialOrd, Ord, Debug, Hash)]
     pub enum OutputFormat { TIFF, JPEG }
 
-    /// `sarpro_hip_speckle_filter`: this library's own (the reference's roadmap names the filters and ships none)
+    /// `sarpro_hip_speckle_filter`: this library's own (the reference's roadmap names the filters and ships none).
+    /// `Frost` and `RefinedLee` are accepted by the `_ext` methods only.
     #[repr(i32)]
     #[derive(Copy, Clone, PartialEq, Eq, PartialOrd, Ord, Debug, Hash)]
-    pub enum SpeckleFilter { Lee = 0, Kuan = 1 }
+    pub enum SpeckleFilter { Lee = 0, Kuan = 1, Frost = 2, RefinedLee = 3 }
 
     /// types.rs:40-45
     #[derive(Copy, Clone, PartialEq, Eq, Debug)]
@@ -546,6 +547,55 @@ impl RasterCore {
         Ok(meta)
     }
 
+    // ------------------------------------------------------------------ Frost and Refined Lee over u16 bands
+    /// Any of the four filters over a u16 band -> f32 of the same shape.  Frost: window 3, 5 or 7 and `damping` > 0 (`looks` is
+    /// ignored); Refined Lee: window 7 and `looks` > 0 (`damping` is ignored); Lee and Kuan: exactly `try_speckle_filter_u16`.
+    pub fn try_speckle_filter_ext_u16(&self, band: &Array2<u16>, filter: SpeckleFilter, window: usize, looks: f64, damping: f64) -> Result<Array2<f32>> {
+        let (rows, cols) = band.dim();
+        let b = band.as_standard_layout();
+        let mut out = vec![0f32; rows * cols];
+        self.chk(unsafe { sys::sarpro_hip_speckle_ext_u16(self.ctx, b.as_ptr(), rows, cols, filter as c_int, window as c_int, looks, damping, out.as_mut_ptr()) })?;
+        Array2::from_shape_vec((rows, cols), out)
+            .map_err(|_| HipError { code: sys::SARPRO_HIP_ERR_SHAPE_MISMATCH, message: "output shape".into() })
+    }
+
+    /// `try_render_multiband_image_speckle_u16` with any of the four filters.
+    pub fn try_render_multiband_image_speckle_ext_u16(&self, band1: &Array2<u16>, band2: &Array2<u16>, filter: SpeckleFilter, window: usize, looks: f64,
+        damping: f64, target_size: Option<usize>, pad: bool, autoscale: AutoscaleStrategy, syn_mode: SyntheticRgbMode, plain_pipeline: bool)
+        -> Result<ProcessedImage> {
+        if band1.dim() != band2.dim() {
+            return Err(HipError { code: sys::SARPRO_HIP_ERR_SHAPE_MISMATCH, message: "band shapes differ".into() });
+        }
+        let (rows, cols) = band1.dim();
+        let (b1, b2) = (band1.as_standard_layout(), band2.as_standard_layout());
+        let (mut fc, mut fr) = (0usize, 0usize);
+        let ts = target_size.unwrap_or(0);
+        self.chk(unsafe { sys::sarpro_hip_resize_output_dims(cols, rows, ts, pad as c_int, &mut fc, &mut fr) })?;
+        let flags = if plain_pipeline { sys::SARPRO_HIP_DUALPOL_PLAIN_PIPELINE } else { 0 };
+        let mut rgb = vec![0u8; fc * fr * 3];
+        let mut meta = zeroed_meta();
+        self.chk(unsafe { sys::sarpro_hip_dualpol_synrgb_speckle_ext_u16(self.ctx, b1.as_ptr(), b2.as_ptr(), rows, cols, filter as c_int, window as c_int,
+            looks, damping, autoscale as c_int, syn_mode as c_int, flags, ts, pad as c_int, rgb.as_mut_ptr(), &mut meta) })?;
+        Ok(ProcessedImage { width: fc, height: fr, bit_depth: BitDepth::U8, format: OutputFormat::JPEG, gray: None, gray16: None,
+            rgb: Some(rgb), gray_band2: None, gray16_band2: None, resize: meta })
+    }
+
+    /// Device-resident forms (`d_*` are device addresses; pitches in elements).
+    pub unsafe fn dev_speckle_ext_u16(&self, d_in: *const u16, rows: usize, cols: usize, in_pitch: usize, filter: SpeckleFilter, window: usize, looks: f64,
+        damping: f64, d_out: *mut f32, out_pitch: usize) -> Result<()> {
+        self.chk(sys::sarpro_hip_speckle_ext_u16_dev(self.ctx, d_in, rows, cols, in_pitch, filter as c_int, window as c_int, looks, damping, d_out, out_pitch))
+    }
+
+    pub unsafe fn dev_dualpol_synrgb_speckle_ext_u16(&self, d_band1: *const u16, d_band2: *const u16, rows: usize, cols: usize, in_pitch: usize,
+        filter: SpeckleFilter, window: usize, looks: f64, damping: f64, strategy: AutoscaleStrategy, mode: SyntheticRgbMode, plain_pipeline: bool,
+        target_size: Option<usize>, pad: bool, d_rgb: *mut u8) -> Result<ResizeMeta> {
+        let flags = if plain_pipeline { sys::SARPRO_HIP_DUALPOL_PLAIN_PIPELINE } else { 0 };
+        let mut meta = zeroed_meta();
+        self.chk(sys::sarpro_hip_dualpol_synrgb_speckle_ext_u16_dev(self.ctx, d_band1, d_band2, rows, cols, in_pitch, filter as c_int, window as c_int,
+            looks, damping, strategy as c_int, mode as c_int, flags, target_size.unwrap_or(0), pad as c_int, d_rgb, &mut meta))?;
+        Ok(meta)
+    }
+
     // ------------------------------------------------------------------ device-pointer entry points (rasters resident in HBM)
     /// `d_*` are device addresses; pitches in elements.  See include/sarpro_hip.h for the stream-ordering contract.
     pub unsafe fn dev_dualpol_synrgb_u16(&self, d_band1: *const u16, d_band2: *const u16, rows: usize, cols: usize, in_pitch: usize,
@@ -854,6 +904,11 @@ pub fn stripe_resized_rows(rows_total: usize, cols: usize, row0: usize, rows_loc
 
 pub fn update_geotransform(gt: &mut [f64; 6], cols: usize, rows: usize, meta: &ResizeMeta) {
     unsafe { sys::sarpro_hip_host_update_geotransform(gt.as_mut_ptr(), cols, rows, meta) }
+}
+
+/// EXP of the Frost filter's definition for x <= 0: the kernels' own sequence of f64 operations, run on the host.
+pub fn speckle_exp(x: f64) -> f64 {
+    unsafe { sys::sarpro_hip_host_speckle_exp(x) }
 }
 
 /// The raster `save_image` hands to its writer (save.rs:23-170 without the encoder).

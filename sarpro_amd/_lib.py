@@ -18,7 +18,7 @@ ERR_HIP, ERR_RCCL, ERR_OOM, ERR_NO_DEVICE, ERR_IO = -4, -5, -6, -7, -8
 ERR_BUFFER_TOO_SMALL = -9
 ERR_UNSUPPORTED = -10
 READ_DEFAULT, READ_AVERAGE, READ_LANCZOS = -1, 0, 1  # sarpro_hip_read_alg
-SPECKLE_LEE, SPECKLE_KUAN = 0, 1  # sarpro_hip_speckle_filter
+SPECKLE_LEE, SPECKLE_KUAN, SPECKLE_FROST, SPECKLE_REFINED_LEE = 0, 1, 2, 3  # sarpro_hip_speckle_filter
 
 
 class Stats(C.Structure):
@@ -120,6 +120,8 @@ SYMBOLS = [
     "sarpro_hip_host_read_lanczos_axis", "sarpro_hip_read_lanczos_u16_dev", "sarpro_hip_read_lanczos_u16",
     "sarpro_hip_speckle_u16_dev", "sarpro_hip_speckle_f32_dev", "sarpro_hip_speckle_u16", "sarpro_hip_speckle_f32",
     "sarpro_hip_dualpol_synrgb_speckle_u16_dev", "sarpro_hip_dualpol_synrgb_speckle_u16",
+    "sarpro_hip_speckle_ext_u16_dev", "sarpro_hip_speckle_ext_u16", "sarpro_hip_dualpol_synrgb_speckle_ext_u16_dev",
+    "sarpro_hip_dualpol_synrgb_speckle_ext_u16", "sarpro_hip_host_speckle_exp",
 ]
 
 if not os.path.exists(LIB_PATH):
@@ -309,3 +311,8 @@ for _n in ("sarpro_hip_speckle_u16", "sarpro_hip_speckle_f32"):
     _proto(_n, _i, _vp, _vp, _sz, _sz, _i, _i, _d, _vp)
 _proto("sarpro_hip_dualpol_synrgb_speckle_u16_dev", _i, _vp, _vp, _vp, _sz, _sz, _sz, _i, _i, _d, _i, _i, _u, _sz, _i, _vp, _M)
 _proto("sarpro_hip_dualpol_synrgb_speckle_u16", _i, _vp, _vp, _vp, _sz, _sz, _i, _i, _d, _i, _i, _u, _sz, _i, _vp, _M)
+_proto("sarpro_hip_speckle_ext_u16_dev", _i, _vp, _vp, _sz, _sz, _sz, _i, _i, _d, _d, _vp, _sz)
+_proto("sarpro_hip_speckle_ext_u16", _i, _vp, _vp, _sz, _sz, _i, _i, _d, _d, _vp)
+_proto("sarpro_hip_dualpol_synrgb_speckle_ext_u16_dev", _i, _vp, _vp, _vp, _sz, _sz, _sz, _i, _i, _d, _d, _i, _i, _u, _sz, _i, _vp, _M)
+_proto("sarpro_hip_dualpol_synrgb_speckle_ext_u16", _i, _vp, _vp, _vp, _sz, _sz, _i, _i, _d, _d, _i, _i, _u, _sz, _i, _vp, _M)
+_proto("sarpro_hip_host_speckle_exp", _d, _d)

@@ -537,6 +537,51 @@ class Context:
                                                                 target_size or 0, int(pad), _vp(d_rgb), C.byref(m)))
         return m
 
+    # ------------------------------------------------------------------ Frost and Refined Lee (u16 bands)
+    def speckle_ext(self, band: np.ndarray, filter: SpeckleFilter, window: int, looks: float = 1.0, damping: float = 1.0) -> np.ndarray:
+        """Any of the four filters over a (rows, cols) uint16 band -> float32 of the same shape.  Frost: window 3, 5 or 7 and `damping`
+        (`looks` is ignored); Refined Lee: window 7 and `looks`; Lee and Kuan: exactly what speckle() gives."""
+        if band.dtype != np.uint16:
+            raise ValueError("band must be uint16")
+        b = np.ascontiguousarray(band)
+        rows, cols = b.shape
+        out = np.empty((rows, cols), np.float32)
+        self._chk(lib.sarpro_hip_speckle_ext_u16(self._h, _vp(b), rows, cols, int(filter), int(window), float(looks), float(damping), _vp(out)))
+        return out
+
+    def dev_speckle_ext_u16(self, d_in: int, rows: int, cols: int, in_pitch: int, filter, window: int, looks: float, damping: float, d_out: int,
+                            out_pitch: int):
+        """speckle_ext with the u16 band (in_pitch elements per row) and the f32 raster (out_pitch elements per row) in device memory."""
+        self._chk(lib.sarpro_hip_speckle_ext_u16_dev(self._h, _vp(d_in), rows, cols, in_pitch, int(filter), int(window), float(looks), float(damping),
+                                                     _vp(d_out), out_pitch))
+
+    def dualpol_synrgb_speckle_ext(self, band1: np.ndarray, band2: np.ndarray, filter, window: int, looks: float, damping: float,
+                                   strategy: AutoscaleStrategy, target_size: int | None, pad: bool, mode: SyntheticRgbMode = SyntheticRgbMode.Default,
+                                   plain_pipeline: bool = False):
+        """dualpol_synrgb_speckle with any of the four filters -> ((final_rows, final_cols, 3) RGB, ResizeMeta)."""
+        from ._lib import ResizeMeta
+        rows, cols = band1.shape
+        fc, fr = resize_output_dims(cols, rows, target_size, pad)
+        rgb = np.empty((fr, fc, 3), np.uint8)
+        m = ResizeMeta()
+        b1 = np.ascontiguousarray(band1, np.uint16)
+        b2 = np.ascontiguousarray(band2, np.uint16)
+        self._chk(lib.sarpro_hip_dualpol_synrgb_speckle_ext_u16(self._h, _vp(b1), _vp(b2), rows, cols, int(filter), int(window), float(looks),
+                                                                float(damping), int(strategy), int(mode), 1 if plain_pipeline else 0,
+                                                                target_size or 0, int(pad), _vp(rgb), C.byref(m)))
+        return rgb, m
+
+    def dev_dualpol_synrgb_speckle_ext(self, d_b1: int, d_b2: int, rows: int, cols: int, in_pitch: int, filter, window: int, looks: float,
+                                       damping: float, strategy: AutoscaleStrategy, target_size: int | None, pad: bool, d_rgb: int,
+                                       mode: SyntheticRgbMode = SyntheticRgbMode.Default, plain_pipeline: bool = False):
+        """dualpol_synrgb_speckle_ext with the bands and the compact final_rows x final_cols x 3 RGB raster in device memory."""
+        from ._lib import ResizeMeta
+        m = ResizeMeta()
+        self._chk(lib.sarpro_hip_dualpol_synrgb_speckle_ext_u16_dev(self._h, _vp(d_b1), _vp(d_b2), rows, cols, in_pitch, int(filter), int(window),
+                                                                    float(looks), float(damping), int(strategy), int(mode),
+                                                                    1 if plain_pipeline else 0, target_size or 0, int(pad), _vp(d_rgb), C.byref(m)))
+        return m
+
     def dualpol_synrgb_read_stream(self, reader, rows: int, cols: int, strategy, target_size: int, pad: bool, mode=SyntheticRgbMode.Default,
                                    plain_pipeline: bool = False, alg: int = _lib.READ_DEFAULT):
         """dualpol_synrgb_read with the bands coming through a row reader (see dualpol_synrgb_stream) -> (RGB, ResizeMeta)."""
@@ -1007,6 +1052,11 @@ def host_stripe_resized_rows(rows_total: int, cols: int, row0: int, rows_local: 
 
 def host_f32_valid_threshold() -> float:
     return float(lib.sarpro_hip_host_f32_valid_threshold())
+
+
+def host_speckle_exp(x: float) -> float:
+    """EXP of the Frost filter's definition for x <= 0, the kernels' own sequence of f64 operations run on the host."""
+    return float(lib.sarpro_hip_host_speckle_exp(float(x)))
 
 
 def host_f32_bin4096_thresholds(min_db: float, max_db: float) -> np.ndarray:

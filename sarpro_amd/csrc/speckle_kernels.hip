@@ -1,4 +1,5 @@
-// speckle_kernels.hip -- adaptive speckle filters (Lee, Kuan) over u16 and f32 bands, f32 out: DESIGN.md 9c.  The definition is this
+// speckle_kernels.hip -- adaptive speckle filters over u16 and f32 bands, f32 out: Lee and Kuan, and over u16 bands Frost and
+// Refined Lee (defined in include/sarpro_hip.h, their kernels are further below).  Lee and Kuan: the definition is this
 // project's own -- the reference's roadmap names the filters (ROADMAP Phase 4) and ships none -- and is fixed operation by operation:
 //   window   k x k around the pixel, clipped to the raster, only VALID samples count (u16: v >= 1; f32: thr <= v < +inf)
 //   centre invalid: the output is (float)v (u16) / the input's bit pattern (f32)
@@ -55,64 +56,93 @@ __device__ __forceinline__ uint32_t speckle_keep(uint32_t w, uint32_t nv, uint32
     return nv >= 2 * p + 2 ? w : (nv == 2 * p + 1 ? (w & 0xffffu) : 0u);
 }
 
-} // namespace
-
-template <uint32_t K, bool VEC>
-__global__ __launch_bounds__(kSpeckleThreads) void k_speckle_u16(SpeckleArgs a) {
-    constexpr uint32_t H = K / 2;
-    constexpr uint32_t ROWS = K == 7 ? 28u : 30u;              // source rows of a stage: a multiple of K
-    constexpr uint32_t VPR = kSpeckleRowLen / 8;               // 16-byte vectors of a stage row (34)
-    constexpr uint32_t NVEC = ROWS * VPR;
-    constexpr uint32_t LOADS = (NVEC + kSpeckleThreads - 1) / kSpeckleThreads; // 4
-    static_assert(ROWS % K == 0, "a stage starts at ring entry 0");
-    static_assert(H <= kSpeckleHaloCols && kSpeckleRowLen % 8 == 0, "the halo is a whole vector");
-    __shared__ uint4 s_stage[2][NVEC];
-    const uint32_t tid = threadIdx.x;
-    const uint32_t nstrips = (a.cols + kSpeckleThreads - 1) / kSpeckleThreads;
-    const uint32_t nrb = (a.rows + a.band_rows - 1) / a.band_rows;
-    uint32_t t = blockIdx.x; // strips fastest: neighbouring workgroups read neighbouring spans of the same source rows
-    const uint32_t strip = t % nstrips;
-    t /= nstrips;
-    const uint32_t rb = t % nrb, band = t / nrb;
-    const uint16_t *src = static_cast<const uint16_t *>(band ? a.src[1] : a.src[0]);
-    float *dst = band ? a.dst[1] : a.dst[0];
-    const uint32_t x0 = strip * kSpeckleThreads;
-    const uint32_t i0 = rb * a.band_rows, i1 = min(i0 + a.band_rows, a.rows);
-    // source rows [ys, ye) of the band, halo included; rows outside the raster are all invalid
-    const int32_t ys = (int32_t)i0 - (int32_t)H, ye = (int32_t)i1 + (int32_t)H;
-    const uint32_t nstages = ((uint32_t)(ye - ys) + ROWS - 1) / ROWS;
-    const bool active = x0 + tid < a.cols;
-    // the lane's vectors of a stage: vector v = tid + q * 256 is vector v % VPR of stage row v / VPR (the same for every stage)
+// the part of the u16 kernels' staging that does not depend on the filter: which vectors of a stage a lane loads, the loads, the LDS writes
+template <uint32_t ROWS, bool VEC>
+struct SpeckleStager {
+    static constexpr uint32_t VPR = kSpeckleRowLen / 8;  // 16-byte vectors of a stage row (34)
+    static constexpr uint32_t NVEC = ROWS * VPR;
+    static constexpr uint32_t LOADS = (NVEC + kSpeckleThreads - 1) / kSpeckleThreads; // 4
     uint32_t lrow[LOADS], lcol[LOADS], lnv[LOADS];
-#pragma unroll
-    for (uint32_t q = 0; q < LOADS; ++q) {
-        const uint32_t v = tid + q * kSpeckleThreads;
-        lrow[q] = v / VPR;
-        const int32_t c = (int32_t)x0 - (int32_t)kSpeckleHaloCols + (int32_t)(v % VPR) * 8;
-        const bool ok = v < NVEC && c >= 0 && (uint32_t)c < a.cols;
-        lcol[q] = ok ? (uint32_t)c : 0u;
-        lnv[q] = ok ? min(8u, a.cols - (uint32_t)c) : 0u;
-    }
     uint4 regs[LOADS];
-    auto load_stage = [&](uint32_t s) {
+    // vector v = tid + q * 256 is vector v % VPR of stage row v / VPR (the same for every stage)
+    __device__ __forceinline__ void init(uint32_t tid, uint32_t x0, uint32_t cols) {
+#pragma unroll
+        for (uint32_t q = 0; q < LOADS; ++q) {
+            const uint32_t v = tid + q * kSpeckleThreads;
+            lrow[q] = v / VPR;
+            const int32_t c = (int32_t)x0 - (int32_t)kSpeckleHaloCols + (int32_t)(v % VPR) * 8;
+            const bool ok = v < NVEC && c >= 0 && (uint32_t)c < cols;
+            lcol[q] = ok ? (uint32_t)c : 0u;
+            lnv[q] = ok ? min(8u, cols - (uint32_t)c) : 0u;
+        }
+    }
+    // source rows [ys, ye) of the band; rows and columns outside the raster read as 0 = invalid
+    __device__ __forceinline__ void load(const uint16_t *src, const SpeckleArgs &a, int32_t ys, int32_t ye, uint32_t s) {
 #pragma unroll
         for (uint32_t q = 0; q < LOADS; ++q) {
             const int32_t y = ys + (int32_t)(s * ROWS + lrow[q]);
             regs[q] = make_uint4(0u, 0u, 0u, 0u);
             if (lnv[q] && y >= 0 && y < ye && (uint32_t)y < a.rows) regs[q] = speckle_fetch8<VEC>(src + (size_t)y * a.in_pitch, lcol[q], a.cols);
         }
-    };
-    auto write_stage = [&](uint32_t half) {
+    }
+    __device__ __forceinline__ void write(uint4 *half, uint32_t tid) const {
 #pragma unroll
         for (uint32_t q = 0; q < LOADS; ++q) {
             const uint32_t v = tid + q * kSpeckleThreads;
             const uint4 r = regs[q];
             if (v < NVEC)
-                s_stage[half][v] = make_uint4(speckle_keep(r.x, lnv[q], 0), speckle_keep(r.y, lnv[q], 1), speckle_keep(r.z, lnv[q], 2), speckle_keep(r.w, lnv[q], 3));
+                half[v] = make_uint4(speckle_keep(r.x, lnv[q], 0), speckle_keep(r.y, lnv[q], 1), speckle_keep(r.z, lnv[q], 2), speckle_keep(r.w, lnv[q], 3));
         }
-    };
-    load_stage(0);
-    write_stage(0);
+    }
+};
+
+// the workgroup's tile: strips fastest (neighbouring workgroups read neighbouring spans of the same source rows), then row bands, then
+// the band of the raster pair
+struct SpeckleTile {
+    const uint16_t *src;
+    float *dst;
+    uint32_t x0, i0, i1;
+};
+
+__device__ __forceinline__ SpeckleTile speckle_tile(const SpeckleArgs &a) {
+    const uint32_t nstrips = (a.cols + kSpeckleThreads - 1) / kSpeckleThreads;
+    const uint32_t nrb = (a.rows + a.band_rows - 1) / a.band_rows;
+    uint32_t t = blockIdx.x;
+    const uint32_t strip = t % nstrips;
+    t /= nstrips;
+    const uint32_t rb = t % nrb, band = t / nrb;
+    SpeckleTile o;
+    o.src = static_cast<const uint16_t *>(band ? a.src[1] : a.src[0]);
+    o.dst = band ? a.dst[1] : a.dst[0];
+    o.x0 = strip * kSpeckleThreads;
+    o.i0 = rb * a.band_rows;
+    o.i1 = min(o.i0 + a.band_rows, a.rows);
+    return o;
+}
+
+} // namespace
+
+template <uint32_t K, bool VEC>
+__global__ __launch_bounds__(kSpeckleThreads) void k_speckle_u16(SpeckleArgs a) {
+    constexpr uint32_t H = K / 2;
+    constexpr uint32_t ROWS = K == 7 ? 28u : 30u;              // source rows of a stage: a multiple of K
+    using Stager = SpeckleStager<ROWS, VEC>;
+    static_assert(ROWS % K == 0, "a stage starts at ring entry 0");
+    static_assert(H <= kSpeckleHaloCols && kSpeckleRowLen % 8 == 0, "the halo is a whole vector");
+    __shared__ uint4 s_stage[2][Stager::NVEC];
+    const uint32_t tid = threadIdx.x;
+    const SpeckleTile tl = speckle_tile(a);
+    const uint16_t *src = tl.src;
+    float *dst = tl.dst;
+    const uint32_t x0 = tl.x0, i0 = tl.i0, i1 = tl.i1;
+    // source rows [ys, ye) of the band, halo included; rows outside the raster are all invalid
+    const int32_t ys = (int32_t)i0 - (int32_t)H, ye = (int32_t)i1 + (int32_t)H;
+    const uint32_t nstages = ((uint32_t)(ye - ys) + ROWS - 1) / ROWS;
+    const bool active = x0 + tid < a.cols;
+    Stager st;
+    st.init(tid, x0, a.cols);
+    st.load(src, a, ys, ye, 0);
+    st.write(s_stage[0], tid);
     __syncthreads();
     // the ring of the last K rows (entry r = rows with (y - ys) % K == r) and the window's totals
     uint32_t e1[K];
@@ -124,7 +154,7 @@ __global__ __launch_bounds__(kSpeckleThreads) void k_speckle_u16(SpeckleArgs a) 
     constexpr uint64_t kS2Mask = (1ull << 40) - 1;
     for (uint32_t s = 0; s < nstages; ++s) {
         const bool more = s + 1 < nstages;
-        if (more) load_stage(s + 1);
+        if (more) st.load(src, a, ys, ye, s + 1);
         const uint16_t *lds = reinterpret_cast<const uint16_t *>(&s_stage[s & 1][0]) + tid + kSpeckleHaloCols - H;
         int32_t y = ys + (int32_t)(s * ROWS);
         for (uint32_t g = 0; g < ROWS / K && y < ye; ++g) {
@@ -165,7 +195,7 @@ __global__ __launch_bounds__(kSpeckleThreads) void k_speckle_u16(SpeckleArgs a) 
                 if (active) dst[(size_t)yo * a.out_pitch + x0 + tid] = out;
             }
         }
-        if (more) write_stage((s + 1) & 1);
+        if (more) st.write(s_stage[(s + 1) & 1], tid);
         __syncthreads();
     }
 }
@@ -227,6 +257,232 @@ __global__ __launch_bounds__(kSpeckleThreads) void k_speckle_f32(SpeckleArgs a) 
     }
 }
 
+// ---------------------------------------------------------------------------- Frost and Refined Lee over u16 bands
+// Both reuse k_speckle_u16's tiling and staging (strips of 256 columns, one lane each, row bands, two LDS stages of 28 / 30 source
+// rows filled by 16-byte loads one stage ahead) and its way of walking a band: per source row a lane reads its k samples from LDS once,
+// pushes what the filter needs of them into a ring of k row entries in registers (statically indexed) and emits the pixel of row y - h.
+namespace {
+
+// index of r2 = dy^2 + dx^2 in the ascending list 0 1 2 4 5 8 9 10 13 18 (windows 3 and 5 use its first 3 and 6 entries)
+__host__ __device__ constexpr uint32_t frost_class(uint32_t r2) { return r2 <= 2 ? r2 : r2 <= 5 ? r2 - 1 : r2 <= 10 ? r2 - 3 : r2 == 13 ? 8u : 9u; }
+
+} // namespace
+
+// Frost.  The weight of a sample depends on its distance from the centre alone, so a pixel needs, per distance class, the sum T_c and
+// the count N_c of the class's valid samples.  A row at vertical offset dy gives its pair sums v[x - j] + v[x + j] (j = 1..h) and its
+// centre sample to the classes dy^2 + j^2, so a ring entry holds the row's h pair words -- sum in bits 0..19, count of valid samples in
+// bits 20.. -- and, as in k_speckle_u16, the row's S2 with its centre sample in bits 40..55.  Per pixel the k ring rows' words are added
+// class by class in packed form (a class has at most 8 samples: T_c <= 8 * 65535 < 2^20), S1 and n are the classes' totals, S2 is kept
+// as a running total; then the f64 tail: a, up to 9 EXPs, the two accumulations in ascending r2, one division.
+template <uint32_t K, bool VEC>
+__global__ __launch_bounds__(kSpeckleThreads) void k_speckle_frost_u16(SpeckleExtArgs xa) {
+    const SpeckleArgs &a = xa.base;
+    constexpr uint32_t H = K / 2;
+    constexpr uint32_t ROWS = K == 7 ? 28u : 30u; // source rows of a stage: a multiple of K
+    constexpr uint32_t NC = frost_class(2 * H * H) + 1;
+    using Stager = SpeckleStager<ROWS, VEC>;
+    static_assert(ROWS % K == 0, "a stage starts at ring entry 0");
+    static_assert(H <= kSpeckleHaloCols && NC <= kFrostMaxClasses, "the halo is a whole vector; dist[] holds every class");
+    __shared__ uint4 s_stage[2][Stager::NVEC];
+    const uint32_t tid = threadIdx.x;
+    const SpeckleTile tl = speckle_tile(a);
+    const int32_t ys = (int32_t)tl.i0 - (int32_t)H, ye = (int32_t)tl.i1 + (int32_t)H;
+    const uint32_t nstages = ((uint32_t)(ye - ys) + ROWS - 1) / ROWS;
+    const bool active = tl.x0 + tid < a.cols;
+    Stager st;
+    st.init(tid, tl.x0, a.cols);
+    st.load(tl.src, a, ys, ye, 0);
+    st.write(s_stage[0], tid);
+    __syncthreads();
+    uint32_t pr[K][H];
+    uint64_t e2[K];
+#pragma unroll
+    for (uint32_t r = 0; r < K; ++r) {
+        e2[r] = 0ull;
+#pragma unroll
+        for (uint32_t j = 0; j < H; ++j) pr[r][j] = 0u;
+    }
+    uint64_t ts2 = 0;
+    constexpr uint64_t kS2Mask = (1ull << 40) - 1;
+    for (uint32_t s = 0; s < nstages; ++s) {
+        const bool more = s + 1 < nstages;
+        if (more) st.load(tl.src, a, ys, ye, s + 1);
+        const uint16_t *lds = reinterpret_cast<const uint16_t *>(&s_stage[s & 1][0]) + tid + kSpeckleHaloCols - H;
+        int32_t y = ys + (int32_t)(s * ROWS);
+        for (uint32_t g = 0; g < ROWS / K && y < ye; ++g) {
+#pragma unroll
+            for (uint32_t r = 0; r < K; ++r, ++y) {
+                if (y >= ye) break; // (uniform)
+                const uint16_t *p = lds + (g * K + r) * kSpeckleRowLen;
+                const uint32_t c = p[H];
+                uint64_t s2 = c * c; // (c < 2^16: the 32-bit product is the whole one)
+#pragma unroll
+                for (uint32_t j = 1; j <= H; ++j) {
+                    const uint32_t lo = p[H - j], hi = p[H + j];
+                    pr[r][j - 1] = (lo + hi) | (((lo != 0u) + (hi != 0u)) << 20);
+                    s2 += lo * lo;
+                    s2 += hi * hi;
+                }
+                ts2 = ts2 + s2 - (e2[r] & kS2Mask);
+                e2[r] = s2 | ((uint64_t)c << 40);
+                const int32_t yo = y - (int32_t)H; // the output row whose window this row completes
+                if (yo < (int32_t)tl.i0) continue; // (uniform)
+                uint32_t cls[NC];
+#pragma unroll
+                for (uint32_t k = 0; k < NC; ++k) cls[k] = 0u;
+#pragma unroll
+                for (uint32_t dyi = 0; dyi < K; ++dyi) { // the window's rows, top to bottom: ring entry (r + 1 + dyi) % K
+                    const uint32_t slot = (r + 1 + dyi) % K, dy = dyi > H ? dyi - H : H - dyi;
+                    const uint32_t cc = (uint32_t)(e2[slot] >> 40);
+                    cls[frost_class(dy * dy)] += cc | ((uint32_t)(cc != 0u) << 20);
+#pragma unroll
+                    for (uint32_t j = 1; j <= H; ++j) cls[frost_class(dy * dy + j * j)] += pr[slot][j - 1];
+                }
+                const uint32_t v = (uint32_t)(e2[(r + K - H) % K] >> 40);
+                uint32_t n = 0, s1 = 0;
+#pragma unroll
+                for (uint32_t k = 0; k < NC; ++k) { n += cls[k] >> 20; s1 += cls[k] & 0xfffffu; }
+                const uint64_t A = (uint64_t)s1 * s1;
+                const uint64_t D = (uint64_t)n * ts2 - A;
+                const double aa = xa.damping * ((double)D / (double)max(A, (uint64_t)1)); // (A >= 1 wherever the centre is valid)
+                double num = (double)(cls[0] & 0xfffffu), den = (double)(cls[0] >> 20);    // 0.0 + 1.0 * T_0 and 0.0 + 1.0 * N_0, bit for bit
+#pragma unroll
+                for (uint32_t k = 1; k < NC; ++k) {
+                    const double w = speckle_exp(-(aa * xa.dist[k]));
+                    num = num + w * (double)(cls[k] & 0xfffffu);
+                    den = den + w * (double)(cls[k] >> 20);
+                }
+                const float out = v ? (float)(num / den) : 0.0f;
+                if (active) tl.dst[(size_t)yo * a.out_pitch + tl.x0 + tid] = out;
+            }
+        }
+        if (more) st.write(s_stage[(s + 1) & 1], tid);
+        __syncthreads();
+    }
+}
+
+// Refined Lee, window 7.  Beside k_speckle_u16's ring and running totals at k = 7 -- which give the fallback, Lee 7 through the same
+// speckle_tail, and tell a directed pixel: 49 valid samples -- a ring entry keeps the row's 7 samples themselves in 4 words, so a pixel
+// has its whole window in registers.  From them, for every pixel: the row sums of three columns -> the nine block sums -> the four
+// gradients -> the direction and the side -> S1 and S2 of the chosen half, each of the 49 samples counted or not by the sign of
+// ax * dx + ay * dy (E: (1, 0), NE: (1, -1), N: (0, -1), NW: (-1, -1); W, SW, S, SE: the negatives).  One tail, fed with the half's
+// (28, S1, A, D) or with the window's.
+template <bool VEC>
+__global__ __launch_bounds__(kSpeckleThreads) void k_speckle_rlee_u16(SpeckleExtArgs xa) {
+    const SpeckleArgs &a = xa.base;
+    constexpr uint32_t K = 7, H = 3, ROWS = 28;
+    using Stager = SpeckleStager<ROWS, VEC>;
+    __shared__ uint4 s_stage[2][Stager::NVEC];
+    const uint32_t tid = threadIdx.x;
+    const SpeckleTile tl = speckle_tile(a);
+    const int32_t ys = (int32_t)tl.i0 - (int32_t)H, ye = (int32_t)tl.i1 + (int32_t)H;
+    const uint32_t nstages = ((uint32_t)(ye - ys) + ROWS - 1) / ROWS;
+    const bool active = tl.x0 + tid < a.cols;
+    Stager st;
+    st.init(tid, tl.x0, a.cols);
+    st.load(tl.src, a, ys, ye, 0);
+    st.write(s_stage[0], tid);
+    __syncthreads();
+    uint32_t e1[K], raw[K][4];
+    uint64_t e2[K];
+#pragma unroll
+    for (uint32_t r = 0; r < K; ++r) {
+        e1[r] = 0u; e2[r] = 0ull;
+#pragma unroll
+        for (uint32_t q = 0; q < 4; ++q) raw[r][q] = 0u;
+    }
+    uint32_t tn = 0, ts1 = 0;
+    uint64_t ts2 = 0;
+    for (uint32_t s = 0; s < nstages; ++s) {
+        const bool more = s + 1 < nstages;
+        if (more) st.load(tl.src, a, ys, ye, s + 1);
+        const uint16_t *lds = reinterpret_cast<const uint16_t *>(&s_stage[s & 1][0]) + tid + kSpeckleHaloCols - H;
+        int32_t y = ys + (int32_t)(s * ROWS);
+        for (uint32_t g = 0; g < ROWS / K && y < ye; ++g) {
+#pragma unroll
+            for (uint32_t r = 0; r < K; ++r, ++y) {
+                if (y >= ye) break; // (uniform)
+                const uint16_t *p = lds + (g * K + r) * kSpeckleRowLen;
+                uint32_t smp[K];
+                uint32_t n = 0, s1 = 0;
+                uint64_t s2 = 0;
+#pragma unroll
+                for (uint32_t j = 0; j < K; ++j) {
+                    smp[j] = p[j];
+                    n += smp[j] != 0u;
+                    s1 += smp[j];
+                    s2 += smp[j] * smp[j]; // (< 2^32: the 32-bit product is the whole one)
+                }
+                tn = tn + n - (e1[r] >> 19);
+                ts1 = ts1 + s1 - (e1[r] & 0x7ffffu);
+                ts2 = ts2 + s2 - e2[r];
+                e1[r] = s1 | (n << 19);
+                e2[r] = s2;
+                raw[r][0] = smp[0] | (smp[1] << 16);
+                raw[r][1] = smp[2] | (smp[3] << 16);
+                raw[r][2] = smp[4] | (smp[5] << 16);
+                raw[r][3] = smp[6];
+                const int32_t yo = y - (int32_t)H; // the output row whose window this row completes
+                if (yo < (int32_t)tl.i0) continue; // (uniform)
+                // sample (dyi, dxi) of the window, 0..6 each: ring entry (r + 1 + dyi) % K
+                auto at = [&](uint32_t dyi, uint32_t dxi) -> uint32_t {
+                    const uint32_t w = raw[(r + 1 + dyi) % K][dxi / 2];
+                    return dxi & 1 ? w >> 16 : w & 0xffffu;
+                };
+                const uint32_t v = at(H, H);
+                // block (i, j): rows 2i..2i+2, columns 2j..2j+2 of the window (named scalars: nothing here may be indexed by a lane's value)
+                auto block = [&](uint32_t i, uint32_t j) -> int32_t {
+                    uint32_t b = 0;
+#pragma unroll
+                    for (uint32_t dy = 0; dy < 3; ++dy)
+#pragma unroll
+                        for (uint32_t dx = 0; dx < 3; ++dx) b += at(2 * i + dy, 2 * j + dx);
+                    return (int32_t)b;
+                };
+                const int32_t b00 = block(0, 0), b01 = block(0, 1), b02 = block(0, 2), b10 = block(1, 0), b11 = block(1, 1), b12 = block(1, 2),
+                              b20 = block(2, 0), b21 = block(2, 1), b22 = block(2, 2);
+                const int32_t g0 = abs((b02 + b12 + b22) - (b00 + b10 + b20));
+                const int32_t g1 = abs((b01 + b02 + b12) - (b10 + b20 + b21));
+                const int32_t g2 = abs((b00 + b01 + b02) - (b20 + b21 + b22));
+                const int32_t g3 = abs((b00 + b01 + b10) - (b12 + b21 + b22));
+                // the largest gradient, the lowest index on a tie; P and Q and P's half-plane (ax, ay)
+                int32_t gm = g0, P = b12, Q = b10, ax = 1, ay = 0;
+                const bool t1 = g1 > gm;
+                gm = t1 ? g1 : gm; P = t1 ? b02 : P; Q = t1 ? b20 : Q; ay = t1 ? -1 : ay;
+                const bool t2 = g2 > gm;
+                gm = t2 ? g2 : gm; P = t2 ? b01 : P; Q = t2 ? b21 : Q; ax = t2 ? 0 : ax; ay = t2 ? -1 : ay;
+                const bool t3 = g3 > gm;
+                P = t3 ? b00 : P; Q = t3 ? b22 : Q; ax = t3 ? -1 : ax; ay = t3 ? -1 : ay;
+                const bool useP = abs(P - b11) <= abs(Q - b11);
+                ax = useP ? ax : -ax;
+                ay = useP ? ay : -ay;
+                uint32_t hs1 = 0;
+                uint64_t hs2 = 0;
+#pragma unroll
+                for (uint32_t dyi = 0; dyi < K; ++dyi) {
+                    const int32_t base = ay * ((int32_t)dyi - (int32_t)H);
+#pragma unroll
+                    for (uint32_t dxi = 0; dxi < K; ++dxi) {
+                        const uint32_t sv = base + ax * ((int32_t)dxi - (int32_t)H) >= 0 ? at(dyi, dxi) : 0u;
+                        hs1 += sv;
+                        hs2 += sv * sv;
+                    }
+                }
+                const bool directed = tn == K * K; // the window lies inside the raster and all its 49 samples are valid
+                const uint32_t fn = directed ? 28u : max(tn, 1u), fs1 = directed ? hs1 : ts1;
+                const uint64_t fs2 = directed ? hs2 : ts2;
+                const uint64_t A = (uint64_t)fs1 * fs1;
+                const uint64_t D = (uint64_t)fn * fs2 - A;
+                float out = speckle_tail((double)fn, (double)fs1, (double)A, (double)D, (double)v, a.cu2, 1.0);
+                out = v ? out : 0.0f;
+                if (active) tl.dst[(size_t)yo * a.out_pitch + tl.x0 + tid] = out;
+            }
+        }
+        if (more) st.write(s_stage[(s + 1) & 1], tid);
+        __syncthreads();
+    }
+}
+
 namespace {
 
 uint64_t speckle_grid(const SpeckleArgs &a, uint32_t band_rows) {
@@ -248,6 +504,30 @@ hipError_t launch_speckle_u16(const SpeckleArgs &a, int window, bool vec, hipStr
     case 11: hipLaunchKernelGGL((k_speckle_u16<5, true>), g, b, 0, s, a); break;
     case 14: hipLaunchKernelGGL((k_speckle_u16<7, false>), g, b, 0, s, a); break;
     case 15: hipLaunchKernelGGL((k_speckle_u16<7, true>), g, b, 0, s, a); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_speckle_ext_u16(const SpeckleExtArgs &xa, bool refined, int window, bool vec, hipStream_t s) {
+    const SpeckleArgs &a = xa.base;
+    if (!a.band_rows || a.band_rows > kSpeckleMaxBandRows || !a.rows || !a.cols || a.rows > kSpeckleMaxDim || a.cols > kSpeckleMaxDim) return hipErrorInvalidValue;
+    const uint64_t grid = speckle_grid(a, a.band_rows);
+    if (!grid || grid > 0x7fffffffull) return hipErrorInvalidValue;
+    const dim3 g((unsigned)grid), b(kSpeckleThreads);
+    if (refined) {
+        if (window != 7) return hipErrorInvalidValue;
+        if (vec) hipLaunchKernelGGL((k_speckle_rlee_u16<true>), g, b, 0, s, xa);
+        else hipLaunchKernelGGL((k_speckle_rlee_u16<false>), g, b, 0, s, xa);
+        return hipGetLastError();
+    }
+    switch (window * 2 + (vec ? 1 : 0)) {
+    case 6: hipLaunchKernelGGL((k_speckle_frost_u16<3, false>), g, b, 0, s, xa); break;
+    case 7: hipLaunchKernelGGL((k_speckle_frost_u16<3, true>), g, b, 0, s, xa); break;
+    case 10: hipLaunchKernelGGL((k_speckle_frost_u16<5, false>), g, b, 0, s, xa); break;
+    case 11: hipLaunchKernelGGL((k_speckle_frost_u16<5, true>), g, b, 0, s, xa); break;
+    case 14: hipLaunchKernelGGL((k_speckle_frost_u16<7, false>), g, b, 0, s, xa); break;
+    case 15: hipLaunchKernelGGL((k_speckle_frost_u16<7, true>), g, b, 0, s, xa); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

@@ -35,3 +35,5 @@ class SyntheticRgbMode(IntEnum):  # types.rs:177-182
 class SpeckleFilter(IntEnum):  # sarpro_hip_speckle_filter: this library's own (the reference's roadmap names the filters, ships none)
     Lee = 0
     Kuan = 1
+    Frost = 2        # the _ext entry points only
+    RefinedLee = 3
