@@ -54,6 +54,14 @@ struct PinnedBuf { // grow-only pinned host allocation, freed with its owner
     template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
 };
 
+// Tables built on the host for one shape (rows, cols, out_rows, out_cols), cached: the device copy, the pinned stage they are built in
+// and uploaded from, and the shape they hold (key[0] == 0: none)
+struct TableCache {
+    DevBuf tab;
+    PinnedBuf host;
+    size_t key[4] = {0, 0, 0, 0};
+};
+
 // Work decomposition for one (scene shape, stripe) -- built once, cached on the context.
 struct StripePlan {
     size_t rows_total = 0, cols = 0, row0 = 0, rows_local = 0;
@@ -231,17 +239,12 @@ struct sarpro_hip_ctx {
     // their RGB raster and the file before it crosses PCIe; pinned: the scan's length (8 bytes) and the header
     sarpro::DevBuf jpeg_coef, jpeg_seg, jpeg_tables, jpeg_band[2], jpeg_rgb, jpeg_file;
     sarpro::PinnedBuf jpeg_host;
-    // downsample on read (read_path.cpp): the two axes' window tables (device, and the pinned stage they are built in) with the shape
-    // they were built for (rows, cols, out_rows, out_cols); the flows' staged u16 bands and their averaged f32 rasters
-    sarpro::DevBuf read_tab, read_src[2], read_band[2];
-    sarpro::PinnedBuf read_host;
-    size_t read_key[4] = {0, 0, 0, 0};
-    // ... and the Lanczos filter's tables (the weights of both axes, then first | count of both axes), cached the same way,
-    // with the widest column window of the cached shape
-    sarpro::DevBuf lanczos_tab;
-    sarpro::PinnedBuf lanczos_host;
-    size_t lanczos_key[4] = {0, 0, 0, 0};
+    // downsample on read (read_path.cpp): the Average filter's window tables of the two axes and the Lanczos filter's (the
+    // weights of both axes, then first | count of both axes), the latter with the widest column window of the cached shape; the
+    // flows' staged u16 bands and their downsampled f32 rasters
+    sarpro::TableCache read_tables, lanczos_tables;
     uint32_t lanczos_col_taps = 0;
+    sarpro::DevBuf read_src[2], read_band[2];
     sarpro::DevBuf speckle_band[2];              // speckle filtering (speckle_path.cpp): the filtered f32 rasters of the host forms and the flows
     sarpro::DevBuf chain_consts;                 // device-resident chain: dB table | suppressed lut_r/g per floor | blue pairs
     sarpro::DevBuf chain_scratch;               // statistics step: per-slice partials | 4096 bins per band

@@ -63,6 +63,12 @@ int bands_u8_table_dev(sarpro_hip_ctx *ctx, const uint16_t *const d_in[], int nb
 // with the needed size in *bytes_out); restart_mcus = 0: the library's interval
 int jpeg_encode_to_host(sarpro_hip_ctx *ctx, const uint8_t *d_pixels, size_t cols, size_t rows, size_t pitch_bytes, int components, unsigned restart_mcus,
                         uint8_t *out, size_t out_capacity, size_t *bytes_out);
+// the flows "two u16 bands in, quicklook RGB out" (read_path.cpp; speckle_path.cpp's host flow takes the same steps): the strategy /
+// mode / flags rules, checked before anything is enqueued or crosses PCIe; the two bands of a scene into read_src[] (pitched) from host
+// rasters or, reader != nullptr, from a row reader through the pinned ring; the RGB raster of jpeg_rgb into host memory, synchronous
+int check_flow(sarpro_hip_ctx *ctx, int strategy, int mode, unsigned flags);
+int stage_bands(sarpro_hip_ctx *ctx, const uint16_t *const host[2], sarpro_hip_row_reader reader, void *reader_user, size_t rows, size_t cols, size_t pitch);
+int rgb_to_host(sarpro_hip_ctx *ctx, uint8_t *rgb_out, size_t bytes);
 int comm_allreduce_sum_u64_async(sarpro_hip_ctx *ctx, uint64_t *d_buf, size_t count);
 void comm_replay_rewind(sarpro_hip_ctx *ctx);   // start of a stripe call: COMM_REPLAY answers from the first recorded buffer again (COMM_RECORD: forget the old ones)
 void comm_saved_release(sarpro_hip_ctx *ctx);

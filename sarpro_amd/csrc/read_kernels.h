@@ -6,6 +6,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "band_walk.h"
+
 namespace sarpro {
 
 // One destination sample of one axis: its window [first, first + count) of source samples and the weights of the window's two edge
@@ -22,11 +24,8 @@ constexpr uint32_t kReadUnits = 4;        // slabs per stage (two stages in LDS:
 constexpr uint32_t kReadMaxBandRows = 32; // destination rows of a workgroup's tile
 
 struct ReadArgs {
-    const uint16_t *src[2]; // nbands rasters of the same shape and pitch
-    float *dst[2];
-    uint32_t nbands;
+    BandRasters io; // u16 in
     uint32_t rows, cols, out_rows, out_cols;
-    size_t in_pitch, out_pitch; // elements
     const ReadAxis *col_tab;    // [out_cols], device
     const ReadAxis *row_tab;    // [out_rows]
     uint32_t strip_cols;        // destination columns per tile, 1..kReadThreads
@@ -47,11 +46,8 @@ constexpr uint32_t kLanczosMaxBandRows = 64; // destination rows of a workgroup'
 constexpr uint32_t kLanczosRing = 8;         // open destination rows per source row: window i is complete before window i + 8 opens
 
 struct LanczosArgs {
-    const uint16_t *src[2]; // nbands rasters of the same shape and pitch
-    float *dst[2];
-    uint32_t nbands;
+    BandRasters io; // u16 in
     uint32_t rows, cols, out_rows, out_cols;
-    size_t in_pitch, out_pitch;            // elements
     const uint32_t *col_first, *col_count; // [out_cols], device
     const uint32_t *row_first, *row_count; // [out_rows]
     const double *col_w, *row_w;           // [out_cols][kLanczosTaps], [out_rows][kLanczosTaps]

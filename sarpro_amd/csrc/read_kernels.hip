@@ -6,39 +6,62 @@
 // Only the integer sum is order-free, and it is exact: every f64 operation happens in the order of the definition, so the result
 // does not depend on the tiling.  (-ffp-contract=off: no product is fused into a sum.)
 //
-// A workgroup owns a tile: a strip of <= 256 destination columns (one lane each) x a band of <= 32 destination rows.  It walks the
-// source rows of the band top to bottom; every row's span of source columns is cut into slabs of kReadChunk samples (one slab for every
-// reduction up to ~12 at full strips; the host narrows the strip for larger reductions; windows wider than a slab -- a reduction beyond
-// 3072, a single destination sample -- simply take several slabs per row: the lane's sums run across them).  kReadUnits slabs make a
-// stage; two stages live in LDS: while the lanes sum stage s out of LDS, the loads of stage s + 1 are in flight into registers and
-// are written to the other half behind the compiler's counted wait, one barrier per stage.  The row tables of the tile sit in LDS so
-// that no global load inside the loop sits behind the prefetch in the memory counter's order.
+// A workgroup owns a tile (band_walk.h): a strip of <= 256 destination columns (one lane each) x a band of <= 32 destination rows.  It
+// walks the source rows of the band top to bottom; every row's span of source columns is cut into slabs of kReadChunk samples (one slab
+// for every reduction up to ~12 at full strips; the host narrows the strip for larger reductions; windows wider than a slab -- a
+// reduction beyond 3072, a single destination sample -- simply take several slabs per row: the lane's sums run across them).  kReadUnits
+// slabs make a stage; two stages live in LDS (SlabStager, which both filters of this file use): while the lanes sum stage s out of LDS,
+// the loads of stage s + 1 are in flight into registers and are written to the other half behind the compiler's counted wait, one
+// barrier per stage.  The row tables of the tile sit in LDS so that no global load inside the loop sits behind the prefetch in the
+// memory counter's order.
 #include "read_kernels.h"
 
 namespace sarpro {
 
 namespace {
 
-constexpr uint32_t kVecPerUnit = kReadChunk / 8;                              // 16-byte vectors of a slab
-constexpr uint32_t kLoadsPerLane = kReadUnits * kVecPerUnit / kReadThreads;   // 6
-static_assert(kReadUnits * kVecPerUnit % kReadThreads == 0, "a stage is a whole number of vectors per lane");
 static_assert((uint64_t)kReadChunk * 65535u < (1ull << 32), "a slab's interior sum fits 32 bits");
 
-// 8 samples from column a (a multiple of 8, a < cols) of a row; samples at and beyond `cols` are never used.  The vector form reads
-// them from the row's padding (a + 8 <= in_pitch, a multiple of 8: rasters are rows x in_pitch elements), with no branch between
-// the loads of a stage; the element form reads them as 0.
-template <bool VEC>
-__device__ __forceinline__ uint4 read_fetch8(const uint16_t *row, uint32_t a, uint32_t cols) {
-    if (VEC) return *reinterpret_cast<const uint4 *>(row + a);
-    uint32_t w[4];
+// The staging of a tile's source rectangle -- columns [cs, ce) (cs on a vector boundary), rows [ys, ye) -- through two LDS stages of
+// UNITS slabs of CHUNK samples: unit u = slab (u % nchunks) of source row ys + u / nchunks.  Which vectors of a stage a lane loads,
+// where the next stage's lie, the loads, the LDS writes.  nchunks == 1 (a literal at the call: Lanczos, Average's ONE): qk stays 0.
+template <uint32_t UNITS, uint32_t CHUNK>
+struct SlabStager {
+    static constexpr uint32_t VPU = CHUNK / 8;                        // 16-byte vectors of a slab
+    static constexpr uint32_t LOADS = UNITS * VPU / kReadThreads;     // Average: 6, Lanczos: 3
+    static_assert(UNITS * VPU % kReadThreads == 0, "a stage is a whole number of vectors per lane");
+    uint32_t cs, ce, ye, nchunks;
+    uint32_t qy[LOADS], qk[LOADS];
+    uint4 regs[LOADS];
+    // vector v = tid + q * 256 is vector v % VPU of the stage's unit v / VPU
+    __device__ __forceinline__ void init(uint32_t tid, uint32_t cs_, uint32_t ce_, uint32_t ys, uint32_t ye_, uint32_t nchunks_) {
+        cs = cs_; ce = ce_; ye = ye_; nchunks = nchunks_;
 #pragma unroll
-    for (uint32_t p = 0; p < 4; ++p) {
-        const uint32_t lo = a + 2 * p < cols ? row[a + 2 * p] : 0u;
-        const uint32_t hi = a + 2 * p + 1 < cols ? row[a + 2 * p + 1] : 0u;
-        w[p] = lo | (hi << 16);
+        for (uint32_t q = 0; q < LOADS; ++q) {
+            const uint32_t ul = (tid + q * kReadThreads) / VPU;
+            qy[q] = ys + ul / nchunks;
+            qk[q] = ul % nchunks;
+        }
     }
-    return make_uint4(w[0], w[1], w[2], w[3]);
-}
+    // the next stage into registers (units past the rectangle: zeros)
+    template <bool VEC>
+    __device__ __forceinline__ void load(uint32_t tid, const uint16_t *src, size_t in_pitch, uint32_t cols) {
+        const uint32_t step_y = UNITS / nchunks, step_k = UNITS % nchunks;
+#pragma unroll
+        for (uint32_t q = 0; q < LOADS; ++q) {
+            const uint32_t iv = (tid + q * kReadThreads) % VPU;
+            const uint32_t col = cs + qk[q] * CHUNK + iv * 8;
+            regs[q] = make_uint4(0u, 0u, 0u, 0u);
+            if (qy[q] < ye && col < ce) regs[q] = fetch8_u16<VEC>(src + (size_t)qy[q] * in_pitch, col, cols);
+            qk[q] += step_k; qy[q] += step_y;
+            if (qk[q] >= nchunks) { qk[q] -= nchunks; ++qy[q]; }
+        }
+    }
+    __device__ __forceinline__ void write(uint32_t tid, uint4 *half) const {
+#pragma unroll
+        for (uint32_t q = 0; q < LOADS; ++q) half[tid + q * kReadThreads] = regs[q];
+    }
+};
 
 } // namespace
 
@@ -46,26 +69,22 @@ __device__ __forceinline__ uint4 read_fetch8(const uint16_t *row, uint32_t a, ui
 // lane's range inside the slab are then constants of the tile, and a row's interior sum fits 32 bits.
 template <bool VEC, bool ONE>
 __global__ __launch_bounds__(kReadThreads) void k_read_average_u16(ReadArgs a) {
-    __shared__ uint4 s_slab[2][kReadUnits][kVecPerUnit];
+    using Stager = SlabStager<kReadUnits, kReadChunk>;
+    __shared__ uint4 s_slab[2][kReadUnits * Stager::VPU];
     __shared__ ReadAxis s_rows[kReadMaxBandRows];
     const uint32_t tid = threadIdx.x;
-    const uint32_t nstrips = (a.out_cols + a.strip_cols - 1) / a.strip_cols;
-    const uint32_t nrb = (a.out_rows + a.band_rows - 1) / a.band_rows;
-    uint32_t t = blockIdx.x; // strips fastest: neighbouring workgroups read neighbouring spans of the same source rows
-    const uint32_t strip = t % nstrips;
-    t /= nstrips;
-    const uint32_t rb = t % nrb, band = t / nrb;
-    const uint16_t *src = band ? a.src[1] : a.src[0];
-    float *dst = band ? a.dst[1] : a.dst[0];
-    const uint32_t j0 = strip * a.strip_cols, j1 = min(j0 + a.strip_cols, a.out_cols);
-    const uint32_t i0 = rb * a.band_rows, i1 = min(i0 + a.band_rows, a.out_rows);
+    const BandTile tl = band_tile(a.io, a.out_cols, a.strip_cols, a.out_rows, a.band_rows);
+    const uint16_t *src = static_cast<const uint16_t *>(tl.src);
+    float *dst = tl.dst;
+    const uint32_t j0 = tl.strip * a.strip_cols, j1 = min(j0 + a.strip_cols, a.out_cols);
+    const uint32_t i0 = tl.rb * a.band_rows, i1 = min(i0 + a.band_rows, a.out_rows);
     if (tid < i1 - i0) s_rows[tid] = a.row_tab[i0 + tid];
     // the tile's source rectangle: columns [cs, ce) (cs on a vector boundary), rows [ys, ye)
     const ReadAxis cfirst = a.col_tab[j0], clast = a.col_tab[j1 - 1], rfirst = a.row_tab[i0], rlast = a.row_tab[i1 - 1];
     const uint32_t cs = cfirst.first & ~7u, ce = clast.first + clast.count;
     const uint32_t ys = rfirst.first, ye = rlast.first + rlast.count;
     const uint32_t nchunks = ONE ? 1u : (ce - cs + kReadChunk - 1) / kReadChunk;
-    const uint32_t nunits = (ye - ys) * nchunks; // unit u = slab (u % nchunks) of source row ys + u / nchunks
+    const uint32_t nunits = (ye - ys) * nchunks;
     const uint32_t nstages = (nunits + kReadUnits - 1) / kReadUnits;
     // the lane's destination column (idle lanes: an empty window beyond every slab)
     const bool active = tid < j1 - j0;
@@ -77,36 +96,10 @@ __global__ __launch_bounds__(kReadThreads) void k_read_average_u16(ReadArgs a) {
         cwf = e.w_first; cwl = e.w_last; cws = e.w_sum;
     }
     const bool wide = c1 - c0 > 1;
-    // the lane's vectors of a stage: vector v = tid + q * 256 is vector v % kVecPerUnit of the stage's unit v / kVecPerUnit
-    uint32_t qy[kLoadsPerLane], qk[kLoadsPerLane];
-#pragma unroll
-    for (uint32_t q = 0; q < kLoadsPerLane; ++q) {
-        const uint32_t ul = (tid + q * kReadThreads) / kVecPerUnit;
-        qy[q] = ys + ul / nchunks;
-        qk[q] = ul % nchunks;
-    }
-    const uint32_t step_y = kReadUnits / nchunks, step_k = kReadUnits % nchunks;
-    uint4 regs[kLoadsPerLane];
-    auto load_stage = [&]() {
-#pragma unroll
-        for (uint32_t q = 0; q < kLoadsPerLane; ++q) {
-            const uint32_t iv = (tid + q * kReadThreads) % kVecPerUnit;
-            const uint32_t col = cs + qk[q] * kReadChunk + iv * 8;
-            regs[q] = make_uint4(0u, 0u, 0u, 0u);
-            if (qy[q] < ye && col < ce) regs[q] = read_fetch8<VEC>(src + (size_t)qy[q] * a.in_pitch, col, a.cols);
-            qk[q] += step_k; qy[q] += step_y;
-            if (qk[q] >= nchunks) { qk[q] -= nchunks; ++qy[q]; }
-        }
-    };
-    auto write_stage = [&](uint32_t half) {
-#pragma unroll
-        for (uint32_t q = 0; q < kLoadsPerLane; ++q) {
-            const uint32_t v = tid + q * kReadThreads;
-            s_slab[half][v / kVecPerUnit][v % kVecPerUnit] = regs[q];
-        }
-    };
-    load_stage();
-    write_stage(0);
+    Stager st;
+    st.init(tid, cs, ce, ys, ye, nchunks);
+    st.template load<VEC>(tid, src, a.io.in_pitch, a.cols);
+    st.write(tid, s_slab[0]);
     __syncthreads();
     // running state: the source row y and its slab k (uniform); the destination row i with its window [r0, r1) (uniform); per lane the
     // row's interior sum and edge samples, and the window's weighted sum T
@@ -118,10 +111,10 @@ __global__ __launch_bounds__(kReadThreads) void k_read_average_u16(ReadArgs a) {
     double T = 0.0;
     for (uint32_t s = 0; s < nstages; ++s) {
         const bool more = s + 1 < nstages;
-        if (more) load_stage();
+        if (more) st.template load<VEC>(tid, src, a.io.in_pitch, a.cols);
         const uint32_t nu = min(kReadUnits, nunits - s * kReadUnits);
         for (uint32_t ul = 0; ul < nu; ++ul) {
-            const uint16_t *slab = reinterpret_cast<const uint16_t *>(&s_slab[s & 1][ul][0]);
+            const uint16_t *slab = reinterpret_cast<const uint16_t *>(&s_slab[s & 1][ul * Stager::VPU]);
             const uint32_t cb = cs + k * kReadChunk, cend = min(cb + kReadChunk, ce);
             const uint32_t lo = max(c0 + 1, cb), hi = min(c1 - 1, cend);
             uint32_t part = 0;
@@ -149,31 +142,30 @@ __global__ __launch_bounds__(kReadThreads) void k_read_average_u16(ReadArgs a) {
                 const double wy = y == r0 ? re.w_first : (y == r1 - 1 ? re.w_last : 1.0);
                 T = T + wy * L;
                 if (y != r1 - 1) break;
-                if (active) dst[(size_t)i * a.out_pitch + j0 + tid] = (float)(T / (cws * re.w_sum));
+                if (active) dst[(size_t)i * a.io.out_pitch + j0 + tid] = (float)(T / (cws * re.w_sum));
                 T = 0.0;
                 if (++i < i1) { re = s_rows[i - i0]; r0 = re.first; r1 = re.first + re.count; } // (a fractional boundary: this row opens the next window too)
             }
             isum = 0;
             k = 0; ++y;
         }
-        if (more) write_stage((s + 1) & 1);
+        if (more) st.write(tid, s_slab[(s + 1) & 1]);
         __syncthreads();
     }
 }
 
 hipError_t launch_read_average_u16(const ReadArgs &a, bool vec, hipStream_t s) {
-    const uint64_t nstrips = (a.out_cols + a.strip_cols - 1) / a.strip_cols, nrb = (a.out_rows + a.band_rows - 1) / a.band_rows;
-    const uint64_t grid = nstrips * nrb * a.nbands;
-    if (!grid || grid > 0x7fffffffull || !a.strip_cols || a.strip_cols > kReadThreads || !a.band_rows || a.band_rows > kReadMaxBandRows) return hipErrorInvalidValue;
+    const unsigned grid = band_grid(a.out_cols, a.strip_cols, a.out_rows, a.band_rows, a.io.nbands);
+    if (!grid || a.strip_cols > kReadThreads || a.band_rows > kReadMaxBandRows) return hipErrorInvalidValue;
 #ifdef SARPRO_READ_ABLATE_GENERIC // (timing variant: the several-slabs form at every shape)
     const bool one = false;
 #else
     const bool one = a.max_span <= kReadChunk;
 #endif
-    if (vec && one) hipLaunchKernelGGL((k_read_average_u16<true, true>), dim3((unsigned)grid), dim3(kReadThreads), 0, s, a);
-    else if (vec) hipLaunchKernelGGL((k_read_average_u16<true, false>), dim3((unsigned)grid), dim3(kReadThreads), 0, s, a);
-    else if (one) hipLaunchKernelGGL((k_read_average_u16<false, true>), dim3((unsigned)grid), dim3(kReadThreads), 0, s, a);
-    else hipLaunchKernelGGL((k_read_average_u16<false, false>), dim3((unsigned)grid), dim3(kReadThreads), 0, s, a);
+    if (vec && one) hipLaunchKernelGGL((k_read_average_u16<true, true>), dim3(grid), dim3(kReadThreads), 0, s, a);
+    else if (vec) hipLaunchKernelGGL((k_read_average_u16<true, false>), dim3(grid), dim3(kReadThreads), 0, s, a);
+    else if (one) hipLaunchKernelGGL((k_read_average_u16<false, true>), dim3(grid), dim3(kReadThreads), 0, s, a);
+    else hipLaunchKernelGGL((k_read_average_u16<false, false>), dim3(grid), dim3(kReadThreads), 0, s, a);
     return hipGetLastError();
 }
 
@@ -187,29 +179,20 @@ hipError_t launch_read_average_u16(const ReadArgs &a, bool vec, hipStream_t s) {
 // and add +0.0: bit-neutral) and adds w_y * H into the open accumulators: destination row i accumulates in ring entry (i - i0) % 8
 // (window i is complete before window i + 8 opens: the host checks the tables), the ring and its bookkeeping statically indexed --
 // the loop over the entries is unrolled and every branch in it is workgroup-uniform.  The row weights of the band sit in LDS.
-namespace {
-constexpr uint32_t kLzVecPerUnit = kLanczosChunk / 8;                                  // 16-byte vectors of a slab
-constexpr uint32_t kLzLoadsPerLane = kLanczosUnits * kLzVecPerUnit / kReadThreads;     // 3
-static_assert(kLanczosUnits * kLzVecPerUnit % kReadThreads == 0, "a stage is a whole number of vectors per lane");
 static_assert(kLanczosChunk % 8 == 0 && kLanczosChunk >= kReadThreads * 5 + 30 + 7 + kLanczosTaps, "a strip's span at a ratio of 5, plus the slack of the unused tap slots");
-} // namespace
 
 template <bool VEC, uint32_t NT>
 __global__ __launch_bounds__(kReadThreads) void k_read_lanczos_u16(LanczosArgs a) {
-    __shared__ uint4 s_slab[2][kLanczosUnits][kLzVecPerUnit];
+    using Stager = SlabStager<kLanczosUnits, kLanczosChunk>;
+    __shared__ uint4 s_slab[2][kLanczosUnits * Stager::VPU];
     __shared__ double s_wrow[kLanczosMaxBandRows * kLanczosTaps];
     __shared__ uint32_t s_rfirst[kLanczosMaxBandRows], s_rend[kLanczosMaxBandRows];
     const uint32_t tid = threadIdx.x;
-    const uint32_t nstrips = (a.out_cols + kReadThreads - 1) / kReadThreads;
-    const uint32_t nrb = (a.out_rows + a.band_rows - 1) / a.band_rows;
-    uint32_t t = blockIdx.x; // strips fastest: neighbouring workgroups read neighbouring spans of the same source rows
-    const uint32_t strip = t % nstrips;
-    t /= nstrips;
-    const uint32_t rb = t % nrb, band = t / nrb;
-    const uint16_t *src = band ? a.src[1] : a.src[0];
-    float *dst = band ? a.dst[1] : a.dst[0];
-    const uint32_t j0 = strip * kReadThreads, j1 = min(j0 + kReadThreads, a.out_cols);
-    const uint32_t i0 = rb * a.band_rows, i1 = min(i0 + a.band_rows, a.out_rows), nb = i1 - i0;
+    const BandTile tl = band_tile(a.io, a.out_cols, kReadThreads, a.out_rows, a.band_rows);
+    const uint16_t *src = static_cast<const uint16_t *>(tl.src);
+    float *dst = tl.dst;
+    const uint32_t j0 = tl.strip * kReadThreads, j1 = min(j0 + kReadThreads, a.out_cols);
+    const uint32_t i0 = tl.rb * a.band_rows, i1 = min(i0 + a.band_rows, a.out_rows), nb = i1 - i0;
     for (uint32_t e = tid; e < nb * kLanczosTaps; e += kReadThreads) s_wrow[e] = a.row_w[(size_t)i0 * kLanczosTaps + e];
     if (tid < nb) {
         const uint32_t f = a.row_first[i0 + tid];
@@ -232,29 +215,10 @@ __global__ __launch_bounds__(kReadThreads) void k_read_lanczos_u16(LanczosArgs a
 #pragma unroll
         for (uint32_t k = 0; k < NT; ++k) w[k] = p[k];
     }
-    // the lane's vectors of a stage: vector v = tid + q * 256 is vector v % kLzVecPerUnit of the stage's unit v / kLzVecPerUnit
-    uint32_t qy[kLzLoadsPerLane];
-#pragma unroll
-    for (uint32_t q = 0; q < kLzLoadsPerLane; ++q) qy[q] = ys + (tid + q * kReadThreads) / kLzVecPerUnit;
-    uint4 regs[kLzLoadsPerLane];
-    auto load_stage = [&]() {
-#pragma unroll
-        for (uint32_t q = 0; q < kLzLoadsPerLane; ++q) {
-            const uint32_t col = cs + (tid + q * kReadThreads) % kLzVecPerUnit * 8;
-            regs[q] = make_uint4(0u, 0u, 0u, 0u);
-            if (qy[q] < ye && col < ce) regs[q] = read_fetch8<VEC>(src + (size_t)qy[q] * a.in_pitch, col, a.cols);
-            qy[q] += kLanczosUnits;
-        }
-    };
-    auto write_stage = [&](uint32_t half) {
-#pragma unroll
-        for (uint32_t q = 0; q < kLzLoadsPerLane; ++q) {
-            const uint32_t v = tid + q * kReadThreads;
-            s_slab[half][v / kLzVecPerUnit][v % kLzVecPerUnit] = regs[q];
-        }
-    };
-    load_stage();
-    write_stage(0);
+    Stager st;
+    st.init(tid, cs, ce, ys, ye, 1u);
+    st.template load<VEC>(tid, src, a.io.in_pitch, a.cols);
+    st.write(tid, s_slab[0]);
     __syncthreads();
     // the ring: entry e holds destination row i0 + li[e] (li[e] % 8 == e) with its window [rf[e], re[e]) of source rows (uniform; no
     // row left: an empty window past every row) and, per lane, the running sum
@@ -268,10 +232,10 @@ __global__ __launch_bounds__(kReadThreads) void k_read_lanczos_u16(LanczosArgs a
     uint32_t y = ys;
     for (uint32_t s = 0; s < nstages; ++s) {
         const bool more = s + 1 < nstages;
-        if (more) load_stage();
+        if (more) st.template load<VEC>(tid, src, a.io.in_pitch, a.cols);
         const uint32_t nu = min(kLanczosUnits, nunits - s * kLanczosUnits);
         for (uint32_t ul = 0; ul < nu; ++ul, ++y) {
-            const uint16_t *slab = reinterpret_cast<const uint16_t *>(&s_slab[s & 1][ul][0]) + off;
+            const uint16_t *slab = reinterpret_cast<const uint16_t *>(&s_slab[s & 1][ul * Stager::VPU]) + off;
 #ifndef SARPRO_LANCZOS_ABLATE_TAPS // (timing variant, tools/build_variant.sh: the pass without the lanes' tap reads and f64 products -- wrong results)
             double H = 0.0;
 #pragma unroll
@@ -284,7 +248,7 @@ __global__ __launch_bounds__(kReadThreads) void k_read_lanczos_u16(LanczosArgs a
                 if (y >= rf[e] && y < re[e]) {
                     acc[e] = acc[e] + s_wrow[li[e] * kLanczosTaps + (y - rf[e])] * H;
                     if (y + 1 == re[e]) { // the window is complete: the one rounding to f32; the entry takes its next destination row
-                        if (active) dst[(size_t)(i0 + li[e]) * a.out_pitch + j0 + tid] = (float)acc[e];
+                        if (active) dst[(size_t)(i0 + li[e]) * a.io.out_pitch + j0 + tid] = (float)acc[e];
                         acc[e] = 0.0;
                         li[e] += kLanczosRing;
                         rf[e] = 0xffffffffu; re[e] = 0xffffffffu;
@@ -293,7 +257,7 @@ __global__ __launch_bounds__(kReadThreads) void k_read_lanczos_u16(LanczosArgs a
                 }
             }
         }
-        if (more) write_stage((s + 1) & 1);
+        if (more) st.write(tid, s_slab[(s + 1) & 1]);
         __syncthreads();
     }
 }
@@ -307,11 +271,10 @@ static void launch_lanczos_class(const LanczosArgs &a, unsigned grid, hipStream_
 }
 
 hipError_t launch_read_lanczos_u16(const LanczosArgs &a, bool vec, hipStream_t s) {
-    const uint64_t nstrips = (a.out_cols + kReadThreads - 1) / kReadThreads, nrb = a.band_rows ? (a.out_rows + a.band_rows - 1) / a.band_rows : 0;
-    const uint64_t grid = nstrips * nrb * a.nbands;
-    if (!grid || grid > 0x7fffffffull || a.band_rows > kLanczosMaxBandRows || !a.col_taps || a.col_taps > kLanczosTaps) return hipErrorInvalidValue;
-    if (vec) launch_lanczos_class<true>(a, (unsigned)grid, s);
-    else launch_lanczos_class<false>(a, (unsigned)grid, s);
+    const unsigned grid = band_grid(a.out_cols, kReadThreads, a.out_rows, a.band_rows, a.io.nbands);
+    if (!grid || a.band_rows > kLanczosMaxBandRows || !a.col_taps || a.col_taps > kLanczosTaps) return hipErrorInvalidValue;
+    if (vec) launch_lanczos_class<true>(a, grid, s);
+    else launch_lanczos_class<false>(a, grid, s);
     return hipGetLastError();
 }
 

@@ -20,6 +20,36 @@
 
 using namespace sarpro;
 
+// ---- the steps every "two u16 bands in, quicklook RGB out" flow takes (internal.h; speckle_path.cpp's host flow takes them too)
+int sarpro::check_flow(sarpro_hip_ctx *ctx, int strategy, int mode, unsigned flags) { // (before anything is enqueued or crosses PCIe)
+    if (strategy < 0 || strategy > SARPRO_STRATEGY_DEFAULT) return fail(ctx, SARPRO_HIP_ERR_INVALID_ARG, "bad strategy");
+    if (mode < 0 || mode > SARPRO_SYNRGB_ENHANCED) return fail(ctx, SARPRO_HIP_ERR_INVALID_ARG, "bad synrgb mode");
+    if (flags & ~SARPRO_HIP_DUALPOL_PLAIN_PIPELINE) return fail(ctx, SARPRO_HIP_ERR_INVALID_ARG, "unknown dual-pol flag");
+    return SARPRO_HIP_OK;
+}
+
+int sarpro::stage_bands(sarpro_hip_ctx *ctx, const uint16_t *const host[2], sarpro_hip_row_reader reader, void *reader_user, size_t rows, size_t cols,
+                        size_t pitch) {
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    for (int b = 0; b < 2; ++b) {
+        HIPCHK(ctx, ctx->read_src[b].reserve(rows * pitch * sizeof(uint16_t)));
+        if (reader) {
+            HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); // the ring's slots are free: the previous band has landed
+            RETCHK(stream_upload_band(ctx, reader, reader_user, b, rows, cols, ctx->read_src[b].as<uint16_t>(), pitch, 0));
+        } else {
+            HIPCHK(ctx, hipMemcpy2DAsync(ctx->read_src[b].p, pitch * 2, host[b], cols * 2, cols * 2, rows, hipMemcpyHostToDevice, ctx->stream));
+        }
+    }
+    return SARPRO_HIP_OK;
+}
+
+int sarpro::rgb_to_host(sarpro_hip_ctx *ctx, uint8_t *rgb_out, size_t bytes) {
+    if (!bytes) return SARPRO_HIP_OK;
+    HIPCHK(ctx, hipMemcpyAsync(rgb_out, ctx->jpeg_rgb.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return SARPRO_HIP_OK;
+}
+
 namespace {
 
 constexpr size_t kReadMaxDim = (size_t)1 << 30;
@@ -94,99 +124,85 @@ bool shape_ok(size_t rows, size_t cols, size_t out_rows, size_t out_cols) {
     return out_rows >= 1 && out_cols >= 1 && out_rows <= rows && out_cols <= cols && rows <= kReadMaxDim && cols <= kReadMaxDim;
 }
 
-// The pass over nb bands of one shape, enqueued on the context's stream (the tables are rebuilt and uploaded when the shape changes).
+// The tables of a shape (key: rows, cols, out_rows, out_cols) in their cache: when the shape changes they are rebuilt in the pinned
+// stage by build(stage) -> a status, timed as the host segment `timer`, and uploaded on the context's stream.  A failing build leaves
+// the cache without a shape.
+template <typename Build>
+int cached_tables(sarpro_hip_ctx *ctx, TableCache &c, const size_t key[4], size_t bytes, const char *timer, Build build) {
+    if (c.tab.p && std::memcmp(key, c.key, sizeof(c.key)) == 0) return SARPRO_HIP_OK;
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); // (an earlier upload may still read the pinned stage on a stream-ordered context)
+    c.key[0] = 0;
+    HIPCHK(ctx, c.host.reserve(bytes));
+    HIPCHK(ctx, c.tab.reserve(bytes));
+    int rc;
+    {
+        HostTimer t(ctx, timer);
+        rc = build(c.host.p);
+    }
+    RETCHK(rc);
+    HIPCHK(ctx, hipMemcpyAsync(c.tab.p, c.host.p, bytes, hipMemcpyHostToDevice, ctx->stream));
+    std::memcpy(c.key, key, sizeof(c.key));
+    return SARPRO_HIP_OK;
+}
+
+// The Average pass over nb bands of one shape, enqueued on the context's stream.
 int average_enqueue(sarpro_hip_ctx *ctx, const uint16_t *const d_in[], int nb, size_t rows, size_t cols, size_t in_pitch, size_t out_rows, size_t out_cols,
                     float *const d_out[], size_t out_pitch) {
-    HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t key[4] = {rows, cols, out_rows, out_cols};
-    const size_t tab_bytes = (out_cols + out_rows) * sizeof(ReadAxis);
-    if (!ctx->read_tab.p || std::memcmp(key, ctx->read_key, sizeof(key)) != 0) {
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); // (an earlier upload may still read the pinned stage on a stream-ordered context)
-        ctx->read_key[0] = 0;
-        HIPCHK(ctx, ctx->read_host.reserve(tab_bytes));
-        HIPCHK(ctx, ctx->read_tab.reserve(tab_bytes));
-        ReadAxis *h = ctx->read_host.as<ReadAxis>();
-        {
-            HostTimer t(ctx, "host:read_tables");
-            read_average_axis(cols, out_cols, h);
-            read_average_axis(rows, out_rows, h + out_cols);
-        }
-        HIPCHK(ctx, hipMemcpyAsync(ctx->read_tab.p, h, tab_bytes, hipMemcpyHostToDevice, ctx->stream));
-        std::memcpy(ctx->read_key, key, sizeof(key));
-    }
+    TableCache &tc = ctx->read_tables;
+    RETCHK(cached_tables(ctx, tc, key, (out_cols + out_rows) * sizeof(ReadAxis), "host:read_tables", [&](void *stage) {
+        ReadAxis *h = static_cast<ReadAxis *>(stage);
+        read_average_axis(cols, out_cols, h);
+        read_average_axis(rows, out_rows, h + out_cols);
+        return SARPRO_HIP_OK;
+    }));
     ReadArgs a{};
-    bool vec = in_pitch % 8 == 0;
-    for (int b = 0; b < nb; ++b) {
-        a.src[b] = d_in[b]; a.dst[b] = d_out[b];
-        vec = vec && (reinterpret_cast<uintptr_t>(d_in[b]) & 15) == 0;
-    }
-    a.nbands = (uint32_t)nb;
+    const bool vec = band_rasters(a.io, d_in, nb, in_pitch, d_out, out_pitch);
     a.rows = (uint32_t)rows; a.cols = (uint32_t)cols; a.out_rows = (uint32_t)out_rows; a.out_cols = (uint32_t)out_cols;
-    a.in_pitch = in_pitch; a.out_pitch = out_pitch;
-    a.col_tab = ctx->read_tab.as<ReadAxis>(); a.row_tab = a.col_tab + out_cols;
+    a.col_tab = tc.tab.as<ReadAxis>(); a.row_tab = a.col_tab + out_cols;
     // a strip's span of source columns fits one LDS slab where the reduction allows it (wider windows take several slabs per row)
     const double r = (double)cols / (double)out_cols;
     a.strip_cols = (uint32_t)std::min<double>(kReadThreads, std::max(1.0, std::floor((double)(kReadChunk - 16) / r)));
     // about 2048 tiles (8 per compute unit), a tile no taller than the row table the kernel keeps in LDS
     const size_t nstrips = (out_cols + a.strip_cols - 1) / a.strip_cols;
     a.band_rows = (uint32_t)std::min<size_t>(kReadMaxBandRows, std::max<size_t>(1, out_rows * nstrips * (size_t)nb / 2048));
-    const ReadAxis *hc = ctx->read_host.as<ReadAxis>(); // (the pinned stage keeps the tables of read_key)
+    const ReadAxis *hc = tc.host.as<ReadAxis>(); // (the pinned stage keeps the tables of the cached shape)
     a.max_span = 0;
     for (size_t j0 = 0; j0 < out_cols; j0 += a.strip_cols) {
         const ReadAxis &l = hc[std::min<size_t>(j0 + a.strip_cols, out_cols) - 1];
         a.max_span = std::max(a.max_span, l.first + l.count - (hc[j0].first & ~7u));
     }
-    {
-        KernelTimer t(ctx, "read_average");
-        HIPCHK(ctx, launch_read_average_u16(a, vec, ctx->stream));
-    }
+    KernelTimer t(ctx, "read_average");
+    HIPCHK(ctx, launch_read_average_u16(a, vec, ctx->stream));
     return SARPRO_HIP_OK;
 }
 
-// The Lanczos pass over nb bands of one shape, enqueued on the context's stream; the tables are cached per shape as the Average
-// filter's are.  Both per-axis ratios are <= 5 (the callers check).
+// The Lanczos pass over nb bands of one shape, enqueued on the context's stream.  Both per-axis ratios are <= 5 (the callers check).
 int lanczos_enqueue(sarpro_hip_ctx *ctx, const uint16_t *const d_in[], int nb, size_t rows, size_t cols, size_t in_pitch, size_t out_rows, size_t out_cols,
                     float *const d_out[], size_t out_pitch) {
-    HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t key[4] = {rows, cols, out_rows, out_cols};
     const size_t nw = (out_cols + out_rows) * kLanczosTaps; // the weights of both axes, then first | count of the columns and of the rows
-    const size_t tab_bytes = nw * sizeof(double) + 2 * (out_cols + out_rows) * sizeof(uint32_t);
-    if (!ctx->lanczos_tab.p || std::memcmp(key, ctx->lanczos_key, sizeof(key)) != 0) {
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); // (an earlier upload may still read the pinned stage on a stream-ordered context)
-        ctx->lanczos_key[0] = 0;
-        HIPCHK(ctx, ctx->lanczos_host.reserve(tab_bytes));
-        HIPCHK(ctx, ctx->lanczos_tab.reserve(tab_bytes));
-        double *hw = ctx->lanczos_host.as<double>();
+    TableCache &tc = ctx->lanczos_tables;
+    RETCHK(cached_tables(ctx, tc, key, nw * sizeof(double) + 2 * (out_cols + out_rows) * sizeof(uint32_t), "host:read_lanczos_tables", [&](void *stage) {
+        double *hw = static_cast<double *>(stage);
         uint32_t *hcf = reinterpret_cast<uint32_t *>(hw + nw), *hcc = hcf + out_cols, *hrf = hcc + out_cols, *hrc = hrf + out_rows;
-        bool ok;
-        {
-            HostTimer t(ctx, "host:read_lanczos_tables");
-            ok = read_lanczos_axis(cols, out_cols, hcf, hcc, hw) && read_lanczos_axis(rows, out_rows, hrf, hrc, hw + out_cols * kLanczosTaps);
-            // what the kernel relies on: a strip's span of source columns (from its first window's vector boundary) and the slack of the
-            // unused tap slots fit one LDS slab; window i of the rows is complete before window i + kLanczosRing opens
-            uint32_t taps = 0;
-            for (size_t j0 = 0; ok && j0 < out_cols; j0 += kReadThreads) {
-                const size_t jl = std::min<size_t>(j0 + kReadThreads, out_cols) - 1;
-                ok = hcf[jl] + hcc[jl] - (hcf[j0] & ~7u) + kLanczosTaps <= kLanczosChunk;
-            }
-            for (size_t j = 0; ok && j < out_cols; ++j) taps = std::max(taps, hcc[j]);
-            for (size_t i = 0; ok && i + kLanczosRing < out_rows; ++i) ok = hrf[i] + hrc[i] <= hrf[i + kLanczosRing];
-            ctx->lanczos_col_taps = taps;
+        bool ok = read_lanczos_axis(cols, out_cols, hcf, hcc, hw) && read_lanczos_axis(rows, out_rows, hrf, hrc, hw + out_cols * kLanczosTaps);
+        // what the kernel relies on: a strip's span of source columns (from its first window's vector boundary) and the slack of the
+        // unused tap slots fit one LDS slab; window i of the rows is complete before window i + kLanczosRing opens
+        uint32_t taps = 0;
+        for (size_t j0 = 0; ok && j0 < out_cols; j0 += kReadThreads) {
+            const size_t jl = std::min<size_t>(j0 + kReadThreads, out_cols) - 1;
+            ok = hcf[jl] + hcc[jl] - (hcf[j0] & ~7u) + kLanczosTaps <= kLanczosChunk;
         }
-        if (!ok) return fail(ctx, SARPRO_HIP_ERR_UNSUPPORTED, "read: the Lanczos windows of this shape do not fit the kernel's tiles");
-        HIPCHK(ctx, hipMemcpyAsync(ctx->lanczos_tab.p, hw, tab_bytes, hipMemcpyHostToDevice, ctx->stream));
-        std::memcpy(ctx->lanczos_key, key, sizeof(key));
-    }
+        for (size_t j = 0; ok && j < out_cols; ++j) taps = std::max(taps, hcc[j]);
+        for (size_t i = 0; ok && i + kLanczosRing < out_rows; ++i) ok = hrf[i] + hrc[i] <= hrf[i + kLanczosRing];
+        ctx->lanczos_col_taps = taps;
+        return ok ? SARPRO_HIP_OK : fail(ctx, SARPRO_HIP_ERR_UNSUPPORTED, "read: the Lanczos windows of this shape do not fit the kernel's tiles");
+    }));
     LanczosArgs a{};
-    bool vec = in_pitch % 8 == 0;
-    for (int b = 0; b < nb; ++b) {
-        a.src[b] = d_in[b]; a.dst[b] = d_out[b];
-        vec = vec && (reinterpret_cast<uintptr_t>(d_in[b]) & 15) == 0;
-    }
-    a.nbands = (uint32_t)nb;
+    const bool vec = band_rasters(a.io, d_in, nb, in_pitch, d_out, out_pitch);
     a.rows = (uint32_t)rows; a.cols = (uint32_t)cols; a.out_rows = (uint32_t)out_rows; a.out_cols = (uint32_t)out_cols;
-    a.in_pitch = in_pitch; a.out_pitch = out_pitch;
-    a.col_w = ctx->lanczos_tab.as<double>(); a.row_w = a.col_w + out_cols * kLanczosTaps;
+    a.col_w = tc.tab.as<double>(); a.row_w = a.col_w + out_cols * kLanczosTaps;
     a.col_first = reinterpret_cast<const uint32_t *>(a.col_w + nw); a.col_count = a.col_first + out_cols;
     a.row_first = a.col_count + out_cols; a.row_count = a.row_first + out_rows;
     a.col_taps = ctx->lanczos_col_taps;
@@ -194,11 +210,16 @@ int lanczos_enqueue(sarpro_hip_ctx *ctx, const uint16_t *const d_in[], int nb, s
     // them, taller ones (up to the LDS row table) once that still leaves about 1024 tiles (4 per compute unit)
     const size_t nstrips = (out_cols + kReadThreads - 1) / kReadThreads;
     a.band_rows = (uint32_t)std::min<size_t>(out_rows, std::min<size_t>(kLanczosMaxBandRows, std::max<size_t>(16, out_rows * nstrips * (size_t)nb / 1024)));
-    {
-        KernelTimer t(ctx, "read_lanczos");
-        HIPCHK(ctx, launch_read_lanczos_u16(a, vec, ctx->stream));
-    }
+    KernelTimer t(ctx, "read_lanczos");
+    HIPCHK(ctx, launch_read_lanczos_u16(a, vec, ctx->stream));
     return SARPRO_HIP_OK;
+}
+
+// the pass of `filter` (SARPRO_READ_AVERAGE or SARPRO_READ_LANCZOS)
+int read_enqueue(sarpro_hip_ctx *ctx, int filter, const uint16_t *const d_in[], int nb, size_t rows, size_t cols, size_t in_pitch, size_t out_rows,
+                 size_t out_cols, float *const d_out[], size_t out_pitch) {
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    return (filter == SARPRO_READ_LANCZOS ? lanczos_enqueue : average_enqueue)(ctx, d_in, nb, rows, cols, in_pitch, out_rows, out_cols, d_out, out_pitch);
 }
 
 // the argument rules of the two sarpro_hip_read_lanczos_u16 forms beyond shape_ok: nothing is enqueued or written on a refusal
@@ -241,24 +262,8 @@ int flow_dev(sarpro_hip_ctx *ctx, const uint16_t *const d_bands[2], size_t rows,
         HIPCHK(ctx, ctx->read_band[b].reserve(orows * opitch * sizeof(float)));
         d_f32[b] = ctx->read_band[b].as<float>();
     }
-    if (filter == SARPRO_READ_LANCZOS) RETCHK(lanczos_enqueue(ctx, d_bands, 2, rows, cols, in_pitch, orows, oc, d_f32, opitch));
-    else RETCHK(average_enqueue(ctx, d_bands, 2, rows, cols, in_pitch, orows, oc, d_f32, opitch));
+    RETCHK(read_enqueue(ctx, filter, d_bands, 2, rows, cols, in_pitch, orows, oc, d_f32, opitch));
     return sarpro_hip_dualpol_synrgb_resized_f32_dev(ctx, d_f32[0], d_f32[1], orows, oc, opitch, strategy, mode, flags, target_size, pad, d_rgb, meta);
-}
-
-// the two bands of a scene into read_src[]: host rasters, or a row reader through the pinned ring
-int stage_bands(sarpro_hip_ctx *ctx, const uint16_t *const host[2], sarpro_hip_row_reader reader, void *reader_user, size_t rows, size_t cols, size_t pitch) {
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    for (int b = 0; b < 2; ++b) {
-        HIPCHK(ctx, ctx->read_src[b].reserve(rows * pitch * sizeof(uint16_t)));
-        if (reader) {
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); // the ring's slots are free: the previous band has landed
-            RETCHK(stream_upload_band(ctx, reader, reader_user, b, rows, cols, ctx->read_src[b].as<uint16_t>(), pitch, 0));
-        } else {
-            HIPCHK(ctx, hipMemcpy2DAsync(ctx->read_src[b].p, pitch * 2, host[b], cols * 2, cols * 2, rows, hipMemcpyHostToDevice, ctx->stream));
-        }
-    }
-    return SARPRO_HIP_OK;
 }
 
 // host bands or a reader -> the RGB raster in jpeg_rgb (the raster of the context the encoder reads)
@@ -267,9 +272,7 @@ int flow_staged(sarpro_hip_ctx *ctx, const uint16_t *const host[2], sarpro_hip_r
     size_t oc = 0, orows = 0;
     int filter = 0;
     RETCHK(flow_shape(ctx, rows, cols, alg, target_size, pad, &oc, &orows, fc, fr, &filter));
-    if (strategy < 0 || strategy > SARPRO_STRATEGY_DEFAULT) return fail(ctx, SARPRO_HIP_ERR_INVALID_ARG, "bad strategy"); // (before the scene crosses PCIe)
-    if (mode < 0 || mode > SARPRO_SYNRGB_ENHANCED) return fail(ctx, SARPRO_HIP_ERR_INVALID_ARG, "bad synrgb mode");
-    if (flags & ~SARPRO_HIP_DUALPOL_PLAIN_PIPELINE) return fail(ctx, SARPRO_HIP_ERR_INVALID_ARG, "unknown dual-pol flag");
+    RETCHK(check_flow(ctx, strategy, mode, flags));
     const size_t pitch = round_up(cols, 64);
     RETCHK(stage_bands(ctx, host, reader, reader_user, rows, cols, pitch));
     HIPCHK(ctx, ctx->jpeg_rgb.reserve(std::max<size_t>(*fc * *fr * 3, 1)));
@@ -277,11 +280,38 @@ int flow_staged(sarpro_hip_ctx *ctx, const uint16_t *const host[2], sarpro_hip_r
     return flow_dev(ctx, d_bands, rows, cols, pitch, oc, orows, filter, strategy, mode, flags, target_size, pad, ctx->jpeg_rgb.as<uint8_t>(), meta);
 }
 
-int rgb_to_host(sarpro_hip_ctx *ctx, uint8_t *rgb_out, size_t bytes) {
-    if (!bytes) return SARPRO_HIP_OK;
-    HIPCHK(ctx, hipMemcpyAsync(rgb_out, ctx->jpeg_rgb.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+// one band through `filter`: the bodies of sarpro_hip_read_{average,lanczos}_u16_dev ...
+int read_dev(sarpro_hip_ctx *ctx, int filter, const uint16_t *d_in, size_t rows, size_t cols, size_t in_pitch, size_t out_rows, size_t out_cols,
+             float *d_out_f32, size_t out_pitch) {
+    if (!ctx) return SARPRO_HIP_ERR_INVALID_ARG;
+    if (!shape_ok(rows, cols, out_rows, out_cols)) return fail(ctx, SARPRO_HIP_ERR_INVALID_ARG, "read: 1 <= out_rows <= rows, 1 <= out_cols <= cols, both up to 2^30");
+    if (!d_in || !d_out_f32) return fail(ctx, SARPRO_HIP_ERR_INVALID_ARG, "null raster");
+    if (in_pitch < cols || out_pitch < out_cols) return fail(ctx, SARPRO_HIP_ERR_INVALID_ARG, "pitch < cols");
+    if (filter == SARPRO_READ_LANCZOS) RETCHK(lanczos_ratio_check(ctx, rows, cols, out_rows, out_cols));
+    timing_reset(ctx);
+    const uint16_t *in[1] = {d_in};
+    float *out[1] = {d_out_f32};
+    RETCHK(read_enqueue(ctx, filter, in, 1, rows, cols, in_pitch, out_rows, out_cols, out, out_pitch));
+    if (ctx->async_dev) { ctx->async_pending = ctx->timing; return SARPRO_HIP_OK; } // stream-ordered: nothing is read back
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return SARPRO_HIP_OK;
+}
+
+// ... and of sarpro_hip_read_{average,lanczos}_u16
+int read_host(sarpro_hip_ctx *ctx, int filter, const uint16_t *in, size_t rows, size_t cols, size_t out_rows, size_t out_cols, float *out_f32) {
+    if (!ctx) return SARPRO_HIP_ERR_INVALID_ARG;
+    if (!shape_ok(rows, cols, out_rows, out_cols)) return fail(ctx, SARPRO_HIP_ERR_INVALID_ARG, "read: 1 <= out_rows <= rows, 1 <= out_cols <= cols, both up to 2^30");
+    if (!in || !out_f32) return fail(ctx, SARPRO_HIP_ERR_INVALID_ARG, "null raster");
+    if (filter == SARPRO_READ_LANCZOS) RETCHK(lanczos_ratio_check(ctx, rows, cols, out_rows, out_cols));
+    timing_reset(ctx);
+    size_t pitch = 0;
+    RETCHK(stage_in_2d(ctx, ctx->read_src[0], in, rows, cols, 2, &pitch));
+    const size_t opitch = round_up(out_cols, 64);
+    HIPCHK(ctx, ctx->read_band[0].reserve(out_rows * opitch * sizeof(float)));
+    const uint16_t *d_in[1] = {ctx->read_src[0].as<uint16_t>()};
+    float *d_out[1] = {ctx->read_band[0].as<float>()};
+    RETCHK(read_enqueue(ctx, filter, d_in, 1, rows, cols, pitch, out_rows, out_cols, d_out, opitch));
+    return fetch_out_2d(ctx, out_f32, d_out[0], opitch * sizeof(float), out_cols * sizeof(float), out_rows);
 }
 
 } // namespace
@@ -311,33 +341,12 @@ extern "C" int sarpro_hip_host_read_average_axis(size_t n_src, size_t n_dst, uin
 
 extern "C" int sarpro_hip_read_average_u16_dev(sarpro_hip_ctx *ctx, const uint16_t *d_in, size_t rows, size_t cols, size_t in_pitch, size_t out_rows,
                                                size_t out_cols, float *d_out_f32, size_t out_pitch) {
-    if (!ctx) return SARPRO_HIP_ERR_INVALID_ARG;
-    if (!shape_ok(rows, cols, out_rows, out_cols)) return fail(ctx, SARPRO_HIP_ERR_INVALID_ARG, "read: 1 <= out_rows <= rows, 1 <= out_cols <= cols, both up to 2^30");
-    if (!d_in || !d_out_f32) return fail(ctx, SARPRO_HIP_ERR_INVALID_ARG, "null raster");
-    if (in_pitch < cols || out_pitch < out_cols) return fail(ctx, SARPRO_HIP_ERR_INVALID_ARG, "pitch < cols");
-    timing_reset(ctx);
-    const uint16_t *in[1] = {d_in};
-    float *out[1] = {d_out_f32};
-    RETCHK(average_enqueue(ctx, in, 1, rows, cols, in_pitch, out_rows, out_cols, out, out_pitch));
-    if (ctx->async_dev) { ctx->async_pending = ctx->timing; return SARPRO_HIP_OK; } // stream-ordered: nothing is read back
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return SARPRO_HIP_OK;
+    return read_dev(ctx, SARPRO_READ_AVERAGE, d_in, rows, cols, in_pitch, out_rows, out_cols, d_out_f32, out_pitch);
 }
 
 extern "C" int sarpro_hip_read_average_u16(sarpro_hip_ctx *ctx, const uint16_t *in, size_t rows, size_t cols, size_t out_rows, size_t out_cols,
                                            float *out_f32) {
-    if (!ctx) return SARPRO_HIP_ERR_INVALID_ARG;
-    if (!shape_ok(rows, cols, out_rows, out_cols)) return fail(ctx, SARPRO_HIP_ERR_INVALID_ARG, "read: 1 <= out_rows <= rows, 1 <= out_cols <= cols, both up to 2^30");
-    if (!in || !out_f32) return fail(ctx, SARPRO_HIP_ERR_INVALID_ARG, "null raster");
-    timing_reset(ctx);
-    size_t pitch = 0;
-    RETCHK(stage_in_2d(ctx, ctx->read_src[0], in, rows, cols, 2, &pitch));
-    const size_t opitch = round_up(out_cols, 64);
-    HIPCHK(ctx, ctx->read_band[0].reserve(out_rows * opitch * sizeof(float)));
-    const uint16_t *d_in[1] = {ctx->read_src[0].as<uint16_t>()};
-    float *d_out[1] = {ctx->read_band[0].as<float>()};
-    RETCHK(average_enqueue(ctx, d_in, 1, rows, cols, pitch, out_rows, out_cols, d_out, opitch));
-    return fetch_out_2d(ctx, out_f32, d_out[0], opitch * sizeof(float), out_cols * sizeof(float), out_rows);
+    return read_host(ctx, SARPRO_READ_AVERAGE, in, rows, cols, out_rows, out_cols, out_f32);
 }
 
 extern "C" int sarpro_hip_host_read_lanczos_axis(size_t n_src, size_t n_dst, uint32_t first[], uint32_t count[], double weights[]) {
@@ -348,35 +357,12 @@ extern "C" int sarpro_hip_host_read_lanczos_axis(size_t n_src, size_t n_dst, uin
 
 extern "C" int sarpro_hip_read_lanczos_u16_dev(sarpro_hip_ctx *ctx, const uint16_t *d_in, size_t rows, size_t cols, size_t in_pitch, size_t out_rows,
                                                size_t out_cols, float *d_out_f32, size_t out_pitch) {
-    if (!ctx) return SARPRO_HIP_ERR_INVALID_ARG;
-    if (!shape_ok(rows, cols, out_rows, out_cols)) return fail(ctx, SARPRO_HIP_ERR_INVALID_ARG, "read: 1 <= out_rows <= rows, 1 <= out_cols <= cols, both up to 2^30");
-    if (!d_in || !d_out_f32) return fail(ctx, SARPRO_HIP_ERR_INVALID_ARG, "null raster");
-    if (in_pitch < cols || out_pitch < out_cols) return fail(ctx, SARPRO_HIP_ERR_INVALID_ARG, "pitch < cols");
-    RETCHK(lanczos_ratio_check(ctx, rows, cols, out_rows, out_cols));
-    timing_reset(ctx);
-    const uint16_t *in[1] = {d_in};
-    float *out[1] = {d_out_f32};
-    RETCHK(lanczos_enqueue(ctx, in, 1, rows, cols, in_pitch, out_rows, out_cols, out, out_pitch));
-    if (ctx->async_dev) { ctx->async_pending = ctx->timing; return SARPRO_HIP_OK; } // stream-ordered: nothing is read back
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return SARPRO_HIP_OK;
+    return read_dev(ctx, SARPRO_READ_LANCZOS, d_in, rows, cols, in_pitch, out_rows, out_cols, d_out_f32, out_pitch);
 }
 
 extern "C" int sarpro_hip_read_lanczos_u16(sarpro_hip_ctx *ctx, const uint16_t *in, size_t rows, size_t cols, size_t out_rows, size_t out_cols,
                                            float *out_f32) {
-    if (!ctx) return SARPRO_HIP_ERR_INVALID_ARG;
-    if (!shape_ok(rows, cols, out_rows, out_cols)) return fail(ctx, SARPRO_HIP_ERR_INVALID_ARG, "read: 1 <= out_rows <= rows, 1 <= out_cols <= cols, both up to 2^30");
-    if (!in || !out_f32) return fail(ctx, SARPRO_HIP_ERR_INVALID_ARG, "null raster");
-    RETCHK(lanczos_ratio_check(ctx, rows, cols, out_rows, out_cols));
-    timing_reset(ctx);
-    size_t pitch = 0;
-    RETCHK(stage_in_2d(ctx, ctx->read_src[0], in, rows, cols, 2, &pitch));
-    const size_t opitch = round_up(out_cols, 64);
-    HIPCHK(ctx, ctx->read_band[0].reserve(out_rows * opitch * sizeof(float)));
-    const uint16_t *d_in[1] = {ctx->read_src[0].as<uint16_t>()};
-    float *d_out[1] = {ctx->read_band[0].as<float>()};
-    RETCHK(lanczos_enqueue(ctx, d_in, 1, rows, cols, pitch, out_rows, out_cols, d_out, opitch));
-    return fetch_out_2d(ctx, out_f32, d_out[0], opitch * sizeof(float), out_cols * sizeof(float), out_rows);
+    return read_host(ctx, SARPRO_READ_LANCZOS, in, rows, cols, out_rows, out_cols, out_f32);
 }
 
 extern "C" int sarpro_hip_dualpol_synrgb_read_u16_dev(sarpro_hip_ctx *ctx, const uint16_t *d_band1, const uint16_t *d_band2, size_t rows, size_t cols,

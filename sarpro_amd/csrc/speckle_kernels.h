@@ -8,6 +8,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "band_walk.h"
+
 namespace sarpro {
 
 constexpr uint32_t kSpeckleThreads = 256;  // one lane per output column of a strip
@@ -19,12 +21,9 @@ constexpr size_t kSpeckleMaxDim = (size_t)1 << 30;
 constexpr uint32_t kFrostMaxClasses = 10;     // distinct dy^2 + dx^2 of a 7 x 7 window: 0 1 2 4 5 8 9 10 13 18 (k = 5: the first 6; k = 3: the first 3)
 
 struct SpeckleArgs {
-    const void *src[2]; // nbands rasters of the same shape and pitch (u16 or f32)
-    float *dst[2];
-    uint32_t nbands;
+    BandRasters io; // u16 or f32 in
     uint32_t rows, cols;
     uint32_t band_rows;         // output rows per tile (u16: 1..kSpeckleMaxBandRows; f32: kSpeckleF32BandRows)
-    size_t in_pitch, out_pitch; // elements
     double cu2;                 // 1 / looks
     double g;                   // Kuan: 1 / (1 + cu2); Lee: exactly 1.0 (w * 1.0 == w)
     float thr;                  // f32: the smallest valid sample

@@ -44,14 +44,8 @@ int speckle_enqueue(sarpro_hip_ctx *ctx, bool f32, const void *const d_in[], int
                     float *const d_out[], size_t out_pitch) {
     HIPCHK(ctx, hipSetDevice(ctx->device));
     SpeckleArgs a{};
-    bool vec = in_pitch % 8 == 0;
-    for (int b = 0; b < nb; ++b) {
-        a.src[b] = d_in[b]; a.dst[b] = d_out[b];
-        vec = vec && (reinterpret_cast<uintptr_t>(d_in[b]) & 15) == 0;
-    }
-    a.nbands = (uint32_t)nb;
+    const bool vec = band_rasters(a.io, d_in, nb, in_pitch, d_out, out_pitch);
     a.rows = (uint32_t)rows; a.cols = (uint32_t)cols;
-    a.in_pitch = in_pitch; a.out_pitch = out_pitch;
     const bool frost = f.filter == SARPRO_SPECKLE_FROST, refined = f.filter == SARPRO_SPECKLE_REFINED_LEE;
     a.cu2 = frost ? 0.0 : 1.0 / f.looks;
     a.g = f.filter == SARPRO_SPECKLE_KUAN ? 1.0 / (1.0 + a.cu2) : 1.0;
@@ -128,13 +122,6 @@ int flow_dev(sarpro_hip_ctx *ctx, const uint16_t *const d_bands[2], size_t rows,
     return sarpro_hip_dualpol_synrgb_resized_f32_dev(ctx, d_f32[0], d_f32[1], rows, cols, opitch, strategy, mode, flags, target_size, pad, d_rgb, meta);
 }
 
-int check_flow(sarpro_hip_ctx *ctx, int strategy, int mode, unsigned flags) { // (before anything is enqueued or crosses PCIe)
-    if (strategy < 0 || strategy > SARPRO_STRATEGY_DEFAULT) return fail(ctx, SARPRO_HIP_ERR_INVALID_ARG, "bad strategy");
-    if (mode < 0 || mode > SARPRO_SYNRGB_ENHANCED) return fail(ctx, SARPRO_HIP_ERR_INVALID_ARG, "bad synrgb mode");
-    if (flags & ~SARPRO_HIP_DUALPOL_PLAIN_PIPELINE) return fail(ctx, SARPRO_HIP_ERR_INVALID_ARG, "unknown dual-pol flag");
-    return SARPRO_HIP_OK;
-}
-
 int flow_entry_dev(sarpro_hip_ctx *ctx, const uint16_t *d_band1, const uint16_t *d_band2, size_t rows, size_t cols, size_t in_pitch, const Filter &f,
                    int strategy, int mode, unsigned flags, size_t target_size, int pad, uint8_t *d_rgb_out, sarpro_hip_resize_meta *meta) {
     if (!ctx) return SARPRO_HIP_ERR_INVALID_ARG;
@@ -156,21 +143,13 @@ int flow_entry_host(sarpro_hip_ctx *ctx, const uint16_t *band1, const uint16_t *
     size_t fc = 0, fr = 0;
     RETCHK(sarpro_hip_resize_output_dims(cols, rows, target_size, pad, &fc, &fr));
     TimingHold hold(ctx);
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    // the bands into read_src[] (pitched), as the read flows stage theirs
     const size_t pitch = round_up(cols, 64);
     const uint16_t *host[2] = {band1, band2};
-    for (int b = 0; b < 2; ++b) {
-        HIPCHK(ctx, ctx->read_src[b].reserve(rows * pitch * sizeof(uint16_t)));
-        HIPCHK(ctx, hipMemcpy2DAsync(ctx->read_src[b].p, pitch * 2, host[b], cols * 2, cols * 2, rows, hipMemcpyHostToDevice, ctx->stream));
-    }
+    RETCHK(stage_bands(ctx, host, nullptr, nullptr, rows, cols, pitch));
     HIPCHK(ctx, ctx->jpeg_rgb.reserve(std::max<size_t>(fc * fr * 3, 1)));
     const uint16_t *d_bands[2] = {ctx->read_src[0].as<uint16_t>(), ctx->read_src[1].as<uint16_t>()};
     RETCHK(flow_dev(ctx, d_bands, rows, cols, pitch, f, strategy, mode, flags, target_size, pad, ctx->jpeg_rgb.as<uint8_t>(), meta));
-    if (!(fc * fr)) return SARPRO_HIP_OK;
-    HIPCHK(ctx, hipMemcpyAsync(rgb_out, ctx->jpeg_rgb.p, fc * fr * 3, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return SARPRO_HIP_OK;
+    return rgb_to_host(ctx, rgb_out, fc * fr * 3);
 }
 
 } // namespace
