@@ -718,11 +718,88 @@ int sarpro_hip_tiff_write_rows(sarpro_hip_tiff_writer *w, size_t row0, size_t nr
 int sarpro_hip_tiff_row_sink(void *user, size_t row0, size_t nrows, const uint8_t *src, size_t src_pitch_bytes);
 int sarpro_hip_tiff_finish(sarpro_hip_tiff_writer *w); /* writes the directory, closes and frees the writer */
 const char *sarpro_hip_tiff_last_error(void);
+/* A TILED file with overviews, uncompressed, in cloud-optimised order: the header; then every directory with its
+ * TileOffsets / TileByteCounts arrays -- the full resolution first, then overviews 1..levels with NewSubfileType = 1, level k of
+ * ceil(w_{k-1} / 2) x ceil(h_{k-1} / 2) pixels --; then the tile data, the SMALLEST level first and the full resolution last, each
+ * level's tiles row-major, edge tiles zero-padded.  Nothing is compressed, so every offset is fixed at creation and the directories
+ * are written then; tile is a multiple of 16 (0: 512); levels 0..16.  Photometric / ExtraSamples / SampleFormat as
+ * sarpro_hip_tiff_create writes them for the same sample count; the geo tags go on directory 0 only.  BigTIFF by the strip writer's
+ * rule applied to the whole file (sarpro_hip_tiff_pyramid_is_bigtiff), or whatever the size when SARPRO_HIP_TIFF_BIGTIFF=YES (or 1)
+ * is in the environment at creation (GDAL's BIGTIFF=YES creation option).  GDAL's ghost "structural metadata" block is NOT written.
+ * Rows of level `level` (0 = the full resolution) may arrive in any order and any chunking: the writer scatters them into their
+ * tiles at the tiles' final offsets; tiles never written read as zeros.  sarpro_hip_tiff_finish completes and closes the file.
+ * sarpro_hip_tiff_write_rows / _row_sink on such a writer write level 0.  The reader of this shim stays strip-only. */
+int sarpro_hip_tiff_create_pyramid(const char *path, uint64_t width, uint64_t height, uint32_t samples, uint32_t bits, uint32_t tile, int levels,
+                                   const double *geotransform6, const sarpro_hip_tiff *geo_keys_from, sarpro_hip_tiff_writer **out);
+int sarpro_hip_tiff_write_level_rows(sarpro_hip_tiff_writer *w, int level, size_t row0, size_t nrows, const void *src, size_t src_pitch_bytes);
+/* The size rule, a pure function: 1 when a pyramid file of this shape is written as BigTIFF (header, directories without geo tags and
+ * tile data, plus 1 MiB, reach 2^32 - 1 bytes: the strip writer's rule), 0 for a classic file, < 0 for bad arguments.
+ * *file_bytes_out (may be NULL): the size of that file without geo tags. */
+int sarpro_hip_tiff_pyramid_is_bigtiff(uint64_t width, uint64_t height, uint32_t samples, uint32_t bits, uint32_t tile, int levels,
+                                       uint64_t *file_bytes_out);
 /* sysfs cpulist syntax ("0-31,64-95") -> CPU numbers, at most max of them; returns the count, -1 on a syntax error.  The batch
  * driver binds each worker thread to the CPUs of its GPU's NUMA node with it (csrc/batch.cpp). */
 int sarpro_hip_host_parse_cpulist(const char *s, int *cpus, int max);
 /* the geotransform of a resized / padded product, save.rs:71-81 (pixel size by cols / final_cols, origin by the padding) */
 void sarpro_hip_host_update_geotransform(double gt[6], size_t cols, size_t rows, const sarpro_hip_resize_meta *m);
+
+/* ================= overview pyramids and the tiled GeoTIFF with overviews =================
+ * The reference's roadmap puts "COG + overviews" (TILED=YES, 512 or 256 blocks, BuildOverviews with AVERAGE) right behind the
+ * plumbing this library mirrors and ships none of it: the definition is this library's own, restated in tests/overviewref.py.
+ * Parity with GDAL's AVERAGE overviews is UNPINNED (GDAL is absent, and it takes fractional source windows at odd sizes); this is
+ * the aligned cascade a COG reader assumes geometrically.
+ *   rasters   u8 or u16 samples (bits 8 / 16), 1..3 components interleaved, row pitch in BYTES
+ *   shapes    level 0 is the raster; level k has w_k = ceil(w_{k-1} / 2), h_k = ceil(h_{k-1} / 2)
+ *   levels    the smallest L >= 0 with max(w_L, h_L) <= min_size (min_size 0: 512), at most 16
+ *   a pixel   of level k, per component: (sum + n / 2) / n in integer arithmetic over the n in {1, 2, 4} samples of the ROUNDED
+ *             level k - 1 at rows 2i, 2i + 1 and columns 2j, 2j + 1 that exist (round half up of the mean)
+ *   SKIP_ZERO 0 is this library's no-data level: a source pixel takes part only if one of its components is non-zero; n = 0
+ *             gives 0 in every component.  ((1,0,0), (0,1,0), (0,0,1) average to (0,0,0): no-data one level up, by definition.)
+ * The result is a function of this definition alone, whatever the levels per launch (context attribute OVR_DEPTH, 1..6: at 6 ONE sweep
+ * over the source writes six levels, at 1 every level is a launch of its own; unset: 2, as fast as 1 and 1.75 x faster than 6 where
+ * measured), pitch or alignment.  A plan places levels 1..L in ONE packed buffer: entry k of its arrays is level k + 1, pitch_bytes =
+ * row bytes rounded up to 16, offset_bytes multiples of 256.  The bytes between a row's end and its pitch and between levels are
+ * never written. */
+#define SARPRO_HIP_OVR_MAX_LEVELS 16
+#define SARPRO_HIP_OVR_SKIP_ZERO 1u
+typedef struct {
+    int levels, components, bits, reserved;
+    size_t cols[16], rows[16], pitch_bytes[16], offset_bytes[16];
+    size_t total_bytes;
+} sarpro_hip_ovr_plan;
+/* No GPU.  Returns the level count (>= 0) and fills *out; SARPRO_HIP_ERR_INVALID_ARG for a zero size, components outside 1..3,
+ * bits other than 8 / 16 or a NULL plan. */
+int sarpro_hip_overview_plan(size_t cols, size_t rows, int components, int bits, size_t min_size, sarpro_hip_ovr_plan *out);
+/* Levels 1..L of the raster at d_src into d_out (plan->total_bytes), both in device memory; kernel-time name "overviews" (one
+ * entry per launch: ceil(L / OVR_DEPTH), OVR_DEPTH unset = 2).  Stream-ordered on the context's stream; synchronous, enqueue-only on a
+ * SARPRO_HIP_CTX_ASYNC_DEV context.  The plan must be one of this raster (a caller may widen pitches and offsets).  A source that
+ * is 16-byte aligned with pitch_bytes % 16 == 0 takes 16-byte loads, any other (aligned to its sample size) element loads with the
+ * same results.  A plan of 0 levels is a successful no-op. */
+int sarpro_hip_overviews_dev(sarpro_hip_ctx *ctx, const void *d_src, size_t cols, size_t rows, size_t pitch_bytes, int components, int bits,
+                             unsigned flags, const sarpro_hip_ovr_plan *plan, void *d_out);
+/* host pointers: a compact source in, the packed buffer out (its padding bytes keep the caller's values) */
+int sarpro_hip_overviews(sarpro_hip_ctx *ctx, const void *src, size_t cols, size_t rows, int components, int bits, unsigned flags,
+                         const sarpro_hip_ovr_plan *plan, void *out);
+/* the same definition on the host: no GPU, one thread, the same packed layout */
+int sarpro_hip_host_overviews(const void *src, size_t cols, size_t rows, size_t pitch_bytes, int components, int bits, unsigned flags,
+                              const sarpro_hip_ovr_plan *plan, void *out);
+/* sarpro_hip_dualpol_synrgb_u16_dev without the per-band u8 outputs, then the pyramid of its RGB raster (components 3, bits 8, pitch
+ * rgb_pitch_px * 3 bytes) into d_ovr_out on the same stream: the RGB is that call's bit for bit, the levels are
+ * sarpro_hip_overviews_dev's of that RGB, stats_out (may be NULL) that call's.  Where the chain is device-resident (every scene that
+ * call runs without host round trips) there is NO host synchronisation between the chain and the sweep: the chain's final read-back
+ * is left enqueued, the sweep goes behind it, and one synchronisation ends the call.  A scene that call orchestrates from the host
+ * (the NO_CHAIN attribute, shapes the chain does not take) synchronises inside the chain as it always does.  Synchronous; on a
+ * SARPRO_HIP_CTX_ASYNC_DEV context with stats_out == NULL the whole call is enqueue-only wherever that call is. */
+int sarpro_hip_dualpol_synrgb_pyramid_u16_dev(sarpro_hip_ctx *ctx, const uint16_t *d_band1, const uint16_t *d_band2, size_t rows, size_t cols,
+                                              size_t in_pitch, int strategy, int mode, uint8_t *d_rgb, size_t rgb_pitch_px,
+                                              sarpro_hip_stats *stats_out, unsigned ovr_flags, const sarpro_hip_ovr_plan *plan, void *d_ovr_out);
+/* Files in, one file out: the two bands through a row reader (sarpro_hip_tiff_pair_reader, a GDAL RasterIO loop, ...) into device
+ * memory, the call above, and the product as a tiled GeoTIFF with overviews at `path` (sarpro_hip_tiff_create_pyramid: tile 0 = 512,
+ * min_size 0 = 512; geotransform6 / geo_keys_from may be NULL).  The levels come down through pinned buffers in row chunks, the
+ * smallest first, so the file is written front to back.  stats_out (may be NULL): sarpro_hip_stats[2]. */
+int sarpro_hip_dualpol_synrgb_stream_u16_cog(sarpro_hip_ctx *ctx, sarpro_hip_row_reader reader, void *reader_user, size_t rows, size_t cols,
+                                             int strategy, int mode, unsigned ovr_flags, uint32_t tile, size_t min_size, const char *path,
+                                             const double *geotransform6, const sarpro_hip_tiff *geo_keys_from, sarpro_hip_stats *stats_out);
 
 /* The same stripe in ONE call per rank, reductions over the library's communicator (sarpro_hip_comm_init
  * must have been called): the device-resident chains with their small all-reduces enqueued on the stream,

@@ -1020,6 +1020,72 @@ impl<M: ?Sized> RasterWriter<M> for PlainTiffWriter {
     }
 }
 
+/// The overview levels of a raster: the plan of the packed buffer and the buffer itself; level `k` (1-based) is
+/// `plan.rows[k - 1]` rows of `plan.pitch_bytes[k - 1]` bytes at `plan.offset_bytes[k - 1]`.
+pub struct Overviews { pub plan: sys::sarpro_hip_ovr_plan, pub packed: Vec<u8> }
+
+impl RasterCore {
+    /// `BuildOverviews` with AVERAGE as this library defines it (the aligned 2 x 2 cascade, round half up; GDAL parity unpinned): `data`
+    /// is `height` rows of `width` pixels of `components` interleaved 8-bit samples -> levels down to a long side <= `min_size`
+    /// (0: 512).  `skip_zero`: 0 is no-data and stays out of the averages.
+    pub fn try_build_overviews(&self, data: &[u8], width: usize, height: usize, components: usize, min_size: usize, skip_zero: bool) -> Result<Overviews> {
+        if data.len() != width * height * components {
+            return Err(HipError { code: sys::SARPRO_HIP_ERR_SHAPE_MISMATCH, message: "raster length is not width * height * components".into() });
+        }
+        let mut plan: sys::sarpro_hip_ovr_plan = unsafe { std::mem::zeroed() };
+        let levels = unsafe { sys::sarpro_hip_overview_plan(width, height, components as c_int, 8, min_size, &mut plan) };
+        if levels < 0 { return Err(HipError { code: levels, message: "bad raster shape".into() }); }
+        let mut packed = vec![0u8; plan.total_bytes];
+        let flags = if skip_zero { sys::SARPRO_HIP_OVR_SKIP_ZERO } else { 0 };
+        self.chk(unsafe { sys::sarpro_hip_overviews(self.ctx, data.as_ptr() as *const c_void, width, height, components as c_int, 8, flags, &plan,
+            packed.as_mut_ptr() as *mut c_void) })?;
+        Ok(Overviews { plan, packed })
+    }
+}
+
+/// The overviews of an interleaved 8-bit raster on the thread's core (see [`RasterCore::try_build_overviews`]).
+pub fn build_overviews(data: &[u8], width: usize, height: usize, components: usize, min_size: usize, skip_zero: bool) -> Result<Overviews> {
+    with_core(|c| c.try_build_overviews(data, width, height, components, min_size, skip_zero))
+}
+
+/// A writer that needs no GDAL for `TILED=YES` + overviews: the RGB or gray u8 raster and its overview levels (built on the device)
+/// as one tiled (Big)TIFF in cloud-optimised order through the library's own writer.
+pub struct PyramidTiffWriter { pub geotransform: Option<[f64; 6]>, pub tile: u32, pub min_size: usize, pub skip_zero: bool }
+
+impl<M: ?Sized> RasterWriter<M> for PyramidTiffWriter {
+    fn write(&mut self, output: &Path, image: &ProcessedImage, _metadata: Option<&M>, _operation: ProcessingOperation)
+        -> std::result::Result<(), Box<dyn std::error::Error>> {
+        let path = std::ffi::CString::new(output.to_string_lossy().as_bytes())?;
+        let (w, h) = (image.width, image.height);
+        let (samples, data): (usize, &Vec<u8>) = if let Some(rgb) = &image.rgb { (3, rgb) } else if let Some(a) = &image.gray { (1, a) } else {
+            return Err("the tiled writer takes an RGB or a gray u8 image".into());
+        };
+        let ovr = build_overviews(data, w, h, samples, self.min_size, self.skip_zero)?;
+        let gt = self.geotransform.map(|mut g| { update_geotransform(&mut g, w, h, &image.resize); g });
+        let mut tw = std::ptr::null_mut();
+        let fail = || -> Box<dyn std::error::Error> {
+            let p = unsafe { sys::sarpro_hip_tiff_last_error() };
+            (if p.is_null() { "tiff error".to_string() } else { unsafe { CStr::from_ptr(p) }.to_string_lossy().into_owned() }).into()
+        };
+        let rc = unsafe { sys::sarpro_hip_tiff_create_pyramid(path.as_ptr(), w as u64, h as u64, samples as u32, 8, self.tile, ovr.plan.levels,
+            gt.as_ref().map_or(std::ptr::null(), |g| g.as_ptr()), std::ptr::null(), &mut tw) };
+        if rc != sys::SARPRO_HIP_OK { return Err(fail()); }
+        let mut rc = sys::SARPRO_HIP_OK;
+        for k in (0..ovr.plan.levels as usize).rev() { // the file's order: the smallest level first
+            if rc == sys::SARPRO_HIP_OK {
+                rc = unsafe { sys::sarpro_hip_tiff_write_level_rows(tw, k as c_int + 1, 0, ovr.plan.rows[k],
+                    ovr.packed[ovr.plan.offset_bytes[k]..].as_ptr() as *const c_void, ovr.plan.pitch_bytes[k]) };
+            }
+        }
+        if rc == sys::SARPRO_HIP_OK {
+            rc = unsafe { sys::sarpro_hip_tiff_write_level_rows(tw, 0, 0, h, data.as_ptr() as *const c_void, w * samples) };
+        }
+        let rc2 = unsafe { sys::sarpro_hip_tiff_finish(tw) };
+        if rc != sys::SARPRO_HIP_OK || rc2 != sys::SARPRO_HIP_OK { return Err(fail()); }
+        Ok(())
+    }
+}
+
 /// One scene of a resident batch: device pointers of its two u16 bands and of its RGB raster (`RasterCore::try_batch_dualpol_synrgb_u16_dev`).
 #[derive(Clone, Copy, Debug)]
 pub struct ResidentScene { pub d_band1: *const u16, pub d_band2: *const u16, pub d_rgb: *mut u8 }

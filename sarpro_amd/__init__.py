@@ -11,5 +11,6 @@ from .api import (LocalGroup, Context, SarproHipError, Stripe, StripeF32, host_f
                   host_f32_valid_threshold, host_speckle_exp, host_f32_bin4096_thresholds, host_f32_level_thresholds,
                   host_f32_clahe_bin_thresholds, host_stats_from_bins4096, resize_output_dims, host_jpeg_header, jpeg_bound,
                   read_output_dims, host_read_average_axis, host_read_lanczos_axis,
-                  batch_dualpol_synrgb_resized, batch_dualpol_synrgb_resized_f32, TiffReader, TiffPair, TiffWriter, host_update_geotransform)
+                  batch_dualpol_synrgb_resized, batch_dualpol_synrgb_resized_f32, TiffReader, TiffPair, TiffWriter, host_update_geotransform,
+                  TiffPyramidWriter, tiff_pyramid_is_bigtiff, overview_plan, overview_levels, host_overviews)
 from ._lib import Stats, F32Partial  # noqa: F401

@@ -19,6 +19,7 @@ ERR_BUFFER_TOO_SMALL = -9
 ERR_UNSUPPORTED = -10
 READ_DEFAULT, READ_AVERAGE, READ_LANCZOS = -1, 0, 1  # sarpro_hip_read_alg
 SPECKLE_LEE, SPECKLE_KUAN, SPECKLE_FROST, SPECKLE_REFINED_LEE = 0, 1, 2, 3  # sarpro_hip_speckle_filter
+OVR_MAX_LEVELS, OVR_SKIP_ZERO = 16, 1  # SARPRO_HIP_OVR_*
 
 
 class Stats(C.Structure):
@@ -48,6 +49,12 @@ class TiffInfo(C.Structure):
         (n, C.c_uint32) for n in ("bits_per_sample", "samples_per_pixel", "sample_format", "planar", "compression",
                                   "big_endian", "bigtiff", "tiled", "has_geo", "tiepoint_count")
     ] + [("pixel_scale", C.c_double * 3), ("tiepoint", C.c_double * 6)]
+
+
+class OvrPlan(C.Structure):
+    """sarpro_hip_ovr_plan: levels 1..L of a raster in one packed buffer (entry k of the arrays is level k + 1)."""
+    _fields_ = [("levels", C.c_int), ("components", C.c_int), ("bits", C.c_int), ("reserved", C.c_int)] + [
+        (n, C.c_size_t * 16) for n in ("cols", "rows", "pitch_bytes", "offset_bytes")] + [("total_bytes", C.c_size_t)]
 
 
 ROW_READER = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t)
@@ -122,6 +129,9 @@ SYMBOLS = [
     "sarpro_hip_dualpol_synrgb_speckle_u16_dev", "sarpro_hip_dualpol_synrgb_speckle_u16",
     "sarpro_hip_speckle_ext_u16_dev", "sarpro_hip_speckle_ext_u16", "sarpro_hip_dualpol_synrgb_speckle_ext_u16_dev",
     "sarpro_hip_dualpol_synrgb_speckle_ext_u16", "sarpro_hip_host_speckle_exp",
+    "sarpro_hip_overview_plan", "sarpro_hip_overviews_dev", "sarpro_hip_overviews", "sarpro_hip_host_overviews",
+    "sarpro_hip_dualpol_synrgb_pyramid_u16_dev", "sarpro_hip_dualpol_synrgb_stream_u16_cog",
+    "sarpro_hip_tiff_create_pyramid", "sarpro_hip_tiff_write_level_rows", "sarpro_hip_tiff_pyramid_is_bigtiff",
 ]
 
 if not os.path.exists(LIB_PATH):
@@ -316,3 +326,13 @@ _proto("sarpro_hip_speckle_ext_u16", _i, _vp, _vp, _sz, _sz, _i, _i, _d, _d, _vp
 _proto("sarpro_hip_dualpol_synrgb_speckle_ext_u16_dev", _i, _vp, _vp, _vp, _sz, _sz, _sz, _i, _i, _d, _d, _i, _i, _u, _sz, _i, _vp, _M)
 _proto("sarpro_hip_dualpol_synrgb_speckle_ext_u16", _i, _vp, _vp, _vp, _sz, _sz, _i, _i, _d, _d, _i, _i, _u, _sz, _i, _vp, _M)
 _proto("sarpro_hip_host_speckle_exp", _d, _d)
+_P = C.POINTER(OvrPlan)
+_proto("sarpro_hip_overview_plan", _i, _sz, _sz, _i, _i, _sz, _P)
+_proto("sarpro_hip_overviews_dev", _i, _vp, _vp, _sz, _sz, _sz, _i, _i, _u, _P, _vp)
+_proto("sarpro_hip_overviews", _i, _vp, _vp, _sz, _sz, _i, _i, _u, _P, _vp)
+_proto("sarpro_hip_host_overviews", _i, _vp, _sz, _sz, _sz, _i, _i, _u, _P, _vp)
+_proto("sarpro_hip_dualpol_synrgb_pyramid_u16_dev", _i, _vp, _vp, _vp, _sz, _sz, _sz, _i, _i, _vp, _sz, _S, _u, _P, _vp)
+_proto("sarpro_hip_dualpol_synrgb_stream_u16_cog", _i, _vp, _vp, _vp, _sz, _sz, _i, _i, _u, C.c_uint32, _sz, C.c_char_p, _vp, _vp, _S)
+_proto("sarpro_hip_tiff_create_pyramid", _i, C.c_char_p, _u64, _u64, C.c_uint32, C.c_uint32, C.c_uint32, _i, _vp, _vp, C.POINTER(_vp))
+_proto("sarpro_hip_tiff_write_level_rows", _i, _vp, _i, _sz, _sz, _vp, _sz)
+_proto("sarpro_hip_tiff_pyramid_is_bigtiff", _i, _u64, _u64, C.c_uint32, C.c_uint32, C.c_uint32, _i, C.POINTER(_u64))

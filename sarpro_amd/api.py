@@ -582,6 +582,58 @@ class Context:
                                                                     1 if plain_pipeline else 0, target_size or 0, int(pad), _vp(d_rgb), C.byref(m)))
         return m
 
+    # ------------------------------------------------------------------ overview pyramids (this library's own definition: DESIGN.md 9g)
+    def overviews(self, raster: np.ndarray, min_size: int = 0, skip_zero: bool = False, plan: "_lib.OvrPlan | None" = None):
+        """The overview levels of a (rows, cols) or (rows, cols, 1..3) uint8 / uint16 raster: the aligned 2 x 2 average cascade, round
+        half up, down to a long side <= min_size (0: 512) -> (plan, packed uint8 buffer of plan.total_bytes; see overview_levels).
+        The buffer starts as 0xA5 bytes wherever the levels do not write (the padding is never written)."""
+        a, rows, cols, comps, bits = _ovr_raster(raster)
+        plan = plan or overview_plan(cols, rows, comps, bits, min_size)
+        out = np.full(max(plan.total_bytes, 1), 0xA5, np.uint8)
+        self._chk(lib.sarpro_hip_overviews(self._h, _vp(a), cols, rows, comps, bits, 1 if skip_zero else 0, C.byref(plan), _vp(out)))
+        return plan, out[:plan.total_bytes]
+
+    def dev_overviews(self, d_src: int, cols: int, rows: int, pitch_bytes: int, components: int, bits: int, plan, d_out: int, skip_zero: bool = False):
+        """overviews with the raster (pitch_bytes per row) and the packed buffer (plan.total_bytes) in device memory."""
+        self._chk(lib.sarpro_hip_overviews_dev(self._h, _vp(d_src), cols, rows, pitch_bytes, components, bits, 1 if skip_zero else 0, C.byref(plan), _vp(d_out)))
+
+    def dev_dualpol_synrgb_pyramid(self, d_b1: int, d_b2: int, rows: int, cols: int, in_pitch: int, strategy, mode, d_rgb: int, rgb_pitch_px: int,
+                                   plan, d_ovr_out: int, skip_zero: bool = False, want_stats: bool = True):
+        """dev_dualpol_synrgb_u16 without the per-band u8 outputs, then the pyramid of its RGB into d_ovr_out on the same stream."""
+        st = (Stats * 2)() if want_stats else None
+        self._chk(lib.sarpro_hip_dualpol_synrgb_pyramid_u16_dev(self._h, _vp(d_b1), _vp(d_b2), rows, cols, in_pitch, int(strategy), int(mode), _vp(d_rgb),
+                                                                rgb_pitch_px, st, 1 if skip_zero else 0, C.byref(plan), _vp(d_ovr_out)))
+        return [st[0], st[1]] if want_stats else None
+
+    def dualpol_synrgb_pyramid(self, band1: np.ndarray, band2: np.ndarray, strategy, mode=SyntheticRgbMode.Default, min_size: int = 0,
+                               skip_zero: bool = False):
+        """Two (rows, cols) uint16 bands -> ((rows, cols, 3) RGB, plan, packed overview buffer): dualpol_synrgb's RGB and its pyramid,
+        staged through device memory by torch (the flow itself is the device-pointer call)."""
+        import torch
+        rows, cols = band1.shape
+        plan = overview_plan(cols, rows, 3, 8, min_size)
+        dev = f"cuda:{self.device}"
+        d1 = torch.from_numpy(np.ascontiguousarray(band1, np.uint16).view(np.int16)).to(dev)
+        d2 = torch.from_numpy(np.ascontiguousarray(band2, np.uint16).view(np.int16)).to(dev)
+        d_rgb = torch.empty((rows, cols, 3), dtype=torch.uint8, device=dev)
+        d_ovr = torch.full((max(plan.total_bytes, 1),), 0xA5, dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize()
+        self.dev_dualpol_synrgb_pyramid(d1.data_ptr(), d2.data_ptr(), rows, cols, cols, strategy, mode, d_rgb.data_ptr(), cols, plan, d_ovr.data_ptr(),
+                                        skip_zero=skip_zero, want_stats=False)
+        self.synchronize()
+        return d_rgb.cpu().numpy(), plan, d_ovr.cpu().numpy()[:plan.total_bytes]
+
+    def dualpol_synrgb_stream_cog(self, reader, rows: int, cols: int, strategy, path: str, mode=SyntheticRgbMode.Default, skip_zero: bool = False,
+                                  tile: int = 0, min_size: int = 0, geotransform=None, geo_keys_from: "TiffReader | None" = None, want_stats: bool = False):
+        """Files in, one file out: the bands through a row reader (see dualpol_synrgb_stream), the RGB and its pyramid on the device,
+        the product at `path` as a tiled GeoTIFF with overviews (TiffPyramidWriter's layout)."""
+        rf, ru, _keep = self._as_reader(reader, cols)
+        gt = (C.c_double * 6)(*geotransform) if geotransform is not None else None
+        st = (Stats * 2)() if want_stats else None
+        self._chk(lib.sarpro_hip_dualpol_synrgb_stream_u16_cog(self._h, rf, ru, rows, cols, int(strategy), int(mode), 1 if skip_zero else 0, tile, min_size,
+                                                               path.encode(), gt, geo_keys_from._h if geo_keys_from else None, st))
+        return [st[0], st[1]] if want_stats else None
+
     def dualpol_synrgb_read_stream(self, reader, rows: int, cols: int, strategy, target_size: int, pad: bool, mode=SyntheticRgbMode.Default,
                                    plain_pipeline: bool = False, alg: int = _lib.READ_DEFAULT):
         """dualpol_synrgb_read with the bands coming through a row reader (see dualpol_synrgb_stream) -> (RGB, ResizeMeta)."""
@@ -1277,6 +1329,85 @@ class TiffWriter:
         h, self._h = self._h, None
         if h:
             _tiff_chk(lib.sarpro_hip_tiff_finish(h))
+
+
+class TiffPyramidWriter:
+    """sarpro_hip_tiff_create_pyramid / write_level_rows / finish: a tiled TIFF with `levels` overviews in cloud-optimised order
+    (level 0 = the full resolution; level k of ceil(w / 2), ceil(h / 2) of level k - 1)."""
+
+    def __init__(self, path: str, width: int, height: int, samples: int, bits: int, levels: int, tile: int = 0, geotransform=None,
+                 geo_keys_from: TiffReader | None = None):
+        h = C.c_void_p()
+        gt = (C.c_double * 6)(*geotransform) if geotransform is not None else None
+        _tiff_chk(lib.sarpro_hip_tiff_create_pyramid(path.encode(), width, height, samples, bits, tile, levels, gt,
+                                                     geo_keys_from._h if geo_keys_from else None, C.byref(h)))
+        self._h = h
+
+    def write_level_rows(self, level: int, row0: int, data: np.ndarray):
+        data = np.ascontiguousarray(data)
+        nrows = data.shape[0]
+        _tiff_chk(lib.sarpro_hip_tiff_write_level_rows(self._h, level, row0, nrows, _vp(data), data.nbytes // max(nrows, 1)))
+
+    def finish(self):
+        h, self._h = self._h, None
+        if h:
+            _tiff_chk(lib.sarpro_hip_tiff_finish(h))
+
+
+def tiff_pyramid_is_bigtiff(width: int, height: int, samples: int, bits: int, tile: int, levels: int):
+    """The tiled writer's size rule (no file is written) -> (bigtiff, file bytes without geo tags)."""
+    n = C.c_uint64(0)
+    rc = lib.sarpro_hip_tiff_pyramid_is_bigtiff(width, height, samples, bits, tile, levels, C.byref(n))
+    if rc < 0:
+        raise SarproHipError(rc, "sarpro_hip_tiff_pyramid_is_bigtiff: bad arguments")
+    return bool(rc), int(n.value)
+
+
+# ---- overview pyramids (DESIGN.md 9g) ----
+def _ovr_raster(raster: np.ndarray):
+    """(contiguous array, rows, cols, components, bits) of a (rows, cols[, 1..3]) uint8 / uint16 raster"""
+    if raster.dtype not in (np.uint8, np.uint16) or raster.ndim not in (2, 3):
+        raise ValueError("overviews take a (rows, cols) or (rows, cols, components) uint8 / uint16 raster")
+    a = np.ascontiguousarray(raster)
+    return a, a.shape[0], a.shape[1], (a.shape[2] if a.ndim == 3 else 1), a.dtype.itemsize * 8
+
+
+def overview_plan(cols: int, rows: int, components: int, bits: int, min_size: int = 0) -> "_lib.OvrPlan":
+    """sarpro_hip_overview_plan (no GPU): plan.levels overview levels, entry k of plan.cols / rows / pitch_bytes / offset_bytes is
+    level k + 1 inside one packed buffer of plan.total_bytes."""
+    plan = _lib.OvrPlan()
+    rc = lib.sarpro_hip_overview_plan(cols, rows, components, bits, min_size, C.byref(plan))
+    if rc < 0:
+        raise SarproHipError(rc, "sarpro_hip_overview_plan: bad arguments")
+    return plan
+
+
+def overview_levels(plan, packed: np.ndarray):
+    """The levels of a packed buffer as arrays: [(rows_k, cols_k, components) views, level 1 first]."""
+    dt = np.uint8 if plan.bits == 8 else np.uint16
+    out = []
+    for k in range(plan.levels):
+        r, c, p, o = plan.rows[k], plan.cols[k], plan.pitch_bytes[k], plan.offset_bytes[k]
+        lv = np.lib.stride_tricks.as_strided(packed[o:o + (r - 1) * p + c * plan.components * dt().itemsize].view(dt),
+                                             (r, c, plan.components), (p, plan.components * dt().itemsize, dt().itemsize), writeable=False)
+        out.append(lv)
+    return out
+
+
+def host_overviews(raster: np.ndarray, min_size: int = 0, skip_zero: bool = False, plan=None, pitch_bytes: int | None = None, shape=None):
+    """sarpro_hip_host_overviews (no GPU, one thread): the definition Context.overviews computes on the device -> (plan, packed buffer,
+    0xA5 wherever nothing is written).  pitch_bytes / shape = (rows, cols, components): `raster` is a pitched buffer of that shape."""
+    if shape is None:
+        a, rows, cols, comps, bits = _ovr_raster(raster)
+        pitch = cols * comps * a.dtype.itemsize
+    else:
+        a, (rows, cols, comps), bits, pitch = np.ascontiguousarray(raster), shape, raster.dtype.itemsize * 8, pitch_bytes
+    plan = plan or overview_plan(cols, rows, comps, bits, min_size)
+    out = np.full(max(plan.total_bytes, 1), 0xA5, np.uint8)
+    rc = lib.sarpro_hip_host_overviews(_vp(a), cols, rows, pitch, comps, bits, 1 if skip_zero else 0, C.byref(plan), _vp(out))
+    if rc != _lib.OK:
+        raise SarproHipError(rc, "sarpro_hip_host_overviews: bad arguments")
+    return plan, out[:plan.total_bytes]
 
 
 def host_update_geotransform(gt, cols: int, rows: int, meta: dict):

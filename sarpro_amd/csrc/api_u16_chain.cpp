@@ -99,6 +99,10 @@ static int chain_tail(U16Job &J, sarpro_hip_stats *stats_out, ChainBandState *d_
     }
     ChainBandState *h_state = ctx->h_small.as<ChainBandState>();
     HIPCHK(ctx, hipMemcpyAsync(h_state, d_state, sizeof(ChainBandState) * (size_t)J.nbands, hipMemcpyDeviceToHost, ctx->stream));
+    if (ctx->defer_chain_tail && !J.reduce) { // the caller enqueues more work behind the chain and completes this tail itself
+        ctx->deferred_tail.kind = 1; ctx->deferred_tail.nb = J.nbands; ctx->deferred_tail.stats_out = stats_out;
+        return SARPRO_HIP_OK;
+    }
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); // the only synchronisation of the chain
     uint32_t hi = 0;
     for (int b = 0; b < J.nbands; ++b) {
@@ -644,6 +648,10 @@ int job_run_chain_levels(U16Job &J, void *const d_out[kMaxBands], size_t out_pit
     }
     ChainBandState *h_state = ctx->h_small.as<ChainBandState>();
     HIPCHK(ctx, hipMemcpyAsync(h_state, d_state, sizeof(ChainBandState) * (size_t)nb, hipMemcpyDeviceToHost, ctx->stream));
+    if (ctx->defer_chain_tail && !u16o && !J.reduce) { // (as chain_tail: u8 levels have no `uncertain` flag to act on)
+        ctx->deferred_tail.kind = 2; ctx->deferred_tail.nb = nb; ctx->deferred_tail.stats_out = stats_out;
+        return SARPRO_HIP_OK;
+    }
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); // the only synchronisation of the chain
     uint32_t hi = 0;
     bool uncertain = false;
@@ -657,6 +665,24 @@ int job_run_chain_levels(U16Job &J, void *const d_out[kMaxBands], size_t out_pit
     if (uncertain) return kRerunOnHostRoute;
     // LDS capacity (bytes per band) of the NEXT scene's DN tables (speed only)
     ctx->chain_levels_cap = std::min<uint32_t>(16384, std::max<uint32_t>(2048, (hi + 1 + 1023) / 1024 * 1024));
+    return SARPRO_HIP_OK;
+}
+
+// The second half of a tail that chain_tail or job_run_chain_levels left enqueued (ctx->defer_chain_tail): the same statements behind
+// the caller's synchronisation.
+int chain_deferred_tail_finish(sarpro_hip_ctx *ctx) {
+    const sarpro_hip_ctx::DeferredTail d = ctx->deferred_tail;
+    ctx->deferred_tail = sarpro_hip_ctx::DeferredTail();
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (!d.kind) return SARPRO_HIP_OK;
+    const ChainBandState *h_state = ctx->h_small.as<ChainBandState>();
+    uint32_t hi = 0;
+    for (int b = 0; b < d.nb; ++b) {
+        if (d.stats_out) d.stats_out[b] = h_state[b].stats;
+        hi = std::max(hi, h_state[b].win_hi);
+    }
+    if (d.kind == 1) ctx->chain_lut_cap = std::min<uint32_t>(16384, std::max<uint32_t>(1024, (hi + 1 + 255) / 256 * 256));
+    else ctx->chain_levels_cap = std::min<uint32_t>(16384, std::max<uint32_t>(2048, (hi + 1 + 1023) / 1024 * 1024));
     return SARPRO_HIP_OK;
 }
 

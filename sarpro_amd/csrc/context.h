@@ -185,7 +185,7 @@ struct BandWorker {
     X(NO_MAILBOX) X(NO_STEP_ESTIMATE) X(F32_ZONES) X(F32_ZONES_DEBUG) X(F32_DIRECT) X(F32_DIRECT_QCAP) X(F32_LEVEL_GENERAL) \
     X(F32_LEVEL_TABLE) X(F32_LEVEL_QCAP) X(F32_HOST_CDFS) X(F32_NO_VEC8) X(NO_BAND_TWIN) X(RESIZE_GENERIC) X(NO_RESIZE_LUT) \
     X(NO_U16_CF) X(U16_ITEM_ROWS) X(PIPE_LANES) X(PIPE_ORDER) X(RGB_GRID) X(PIECE_GRID) X(COMM_RECORD) X(COMM_REPLAY) X(NO_SPEC_RESCALE) X(RGB_TAIL_ROWS) X(RGB_TAIL_ITEM_ROWS) \
-    X(READ_LANCZOS)
+    X(READ_LANCZOS) X(OVR_DEPTH)
 namespace sarpro {
 enum Attr : int {
 #define X(n) A_##n,
@@ -246,10 +246,20 @@ struct sarpro_hip_ctx {
     uint32_t lanczos_col_taps = 0;
     sarpro::DevBuf read_src[2], read_band[2];
     sarpro::DevBuf speckle_band[2];              // speckle filtering (speckle_path.cpp): the filtered f32 rasters of the host forms and the flows
+    // overview pyramids (overview_path.cpp): the staged source and the packed levels of the host-pointer form and of the file flow, and
+    // the pinned slots the file flow brings the levels down through
+    sarpro::DevBuf ovr_src, ovr_out;
+    sarpro::PinnedBuf ovr_host;
     sarpro::DevBuf chain_consts;                 // device-resident chain: dB table | suppressed lut_r/g per floor | blue pairs
     sarpro::DevBuf chain_scratch;               // statistics step: per-slice partials | 4096 bins per band
     sarpro::DevBuf chain_state;                  // ChainBandState[2] | resc[2][256] | identity[2] | floor
     bool chain_ready = false;
+    // sarpro_hip_dualpol_synrgb_pyramid_u16_dev (overview_path.cpp): while defer_chain_tail is set a device-resident chain leaves its final
+    // read-back (statistics, the next scene's LDS capacities) ENQUEUED into h_small instead of synchronising, and notes it here
+    // (kind 1: job_run_chain's tail, 2: job_run_chain_levels'); the caller enqueues its own work behind and completes it with
+    // chain_deferred_tail_finish (internal.h), the one synchronisation of the call
+    bool defer_chain_tail = false;
+    struct DeferredTail { int kind = 0, nb = 0; sarpro_hip_stats *stats_out = nullptr; } deferred_tail;
     bool blue_factors_ok = false;                // chain_consts holds the verified blue factor tables (host_logic: synrgb_blue_factors_supp)
     uint32_t chain_levels_cap = 4096;            // LDS bytes per band of the fused pass's DN tables (percentile chain)
     uint32_t chain_lut_cap = 4096;               // LDS capacity (entries) of the apply kernel's offset table

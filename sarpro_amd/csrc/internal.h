@@ -69,6 +69,9 @@ int jpeg_encode_to_host(sarpro_hip_ctx *ctx, const uint8_t *d_pixels, size_t col
 int check_flow(sarpro_hip_ctx *ctx, int strategy, int mode, unsigned flags);
 int stage_bands(sarpro_hip_ctx *ctx, const uint16_t *const host[2], sarpro_hip_row_reader reader, void *reader_user, size_t rows, size_t cols, size_t pitch);
 int rgb_to_host(sarpro_hip_ctx *ctx, uint8_t *rgb_out, size_t bytes);
+// completes a chain tail left enqueued under ctx->defer_chain_tail (context.h): synchronises the stream, hands out the statistics and
+// sizes the next scene's LDS tables as the chain's own tail does; a no-op status when nothing was deferred (api_u16_chain.cpp)
+int chain_deferred_tail_finish(sarpro_hip_ctx *ctx);
 int comm_allreduce_sum_u64_async(sarpro_hip_ctx *ctx, uint64_t *d_buf, size_t count);
 void comm_replay_rewind(sarpro_hip_ctx *ctx);   // start of a stripe call: COMM_REPLAY answers from the first recorded buffer again (COMM_RECORD: forget the old ones)
 void comm_saved_release(sarpro_hip_ctx *ctx);

@@ -8,9 +8,13 @@
 // RowsPerStrip), 8- or 16-bit unsigned samples, chunky or planar.  Tiles, compression, palettes and sub-IFDs are
 // reported as SARPRO_HIP_ERR_IO with a message, not guessed at.  GeoTIFF: ModelPixelScale / ModelTiepoint are
 // parsed and written, the GeoKey directory and its double / ASCII parameter tags are carried over verbatim.
+#include <unistd.h>
+
 #include <algorithm>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -21,7 +25,7 @@ namespace {
 enum : uint16_t {
     kImageWidth = 256, kImageLength = 257, kBitsPerSample = 258, kCompression = 259, kPhotometric = 262,
     kStripOffsets = 273, kSamplesPerPixel = 277, kRowsPerStrip = 278, kStripByteCounts = 279, kPlanarConfig = 284,
-    kExtraSamples = 338, kSampleFormat = 339, kTileWidth = 322,
+    kExtraSamples = 338, kSampleFormat = 339, kTileWidth = 322, kTileLength = 323, kTileOffsets = 324, kTileByteCounts = 325, kNewSubfileType = 254,
     kModelPixelScale = 33550, kModelTiepoint = 33922, kGeoKeyDirectory = 34735, kGeoDoubleParams = 34736,
     kGeoAsciiParams = 34737,
 };
@@ -259,6 +263,12 @@ struct sarpro_hip_tiff_writer {
     std::vector<uint16_t> geo_keys;
     std::vector<double> geo_doubles;
     std::string geo_ascii;
+    // a tiled file with overviews (sarpro_hip_tiff_create_pyramid): level 0 = the full resolution; the directories are on disk already
+    struct Level { uint64_t w = 0, h = 0, tiles_x = 0, tiles_y = 0, data_off = 0; };
+    bool pyramid = false;
+    uint64_t tile = 0, tile_bytes = 0;
+    std::vector<Level> lev;
+    std::vector<uint8_t> scratch;
 };
 
 extern "C" int sarpro_hip_tiff_create(const char *path, uint64_t width, uint64_t height, uint32_t samples, uint32_t bits,
@@ -288,6 +298,7 @@ extern "C" int sarpro_hip_tiff_create(const char *path, uint64_t width, uint64_t
 
 extern "C" int sarpro_hip_tiff_write_rows(sarpro_hip_tiff_writer *w, size_t row0, size_t nrows, const void *src, size_t src_pitch_bytes) {
     if (!w || !src) return SARPRO_HIP_ERR_INVALID_ARG;
+    if (w->pyramid) return sarpro_hip_tiff_write_level_rows(w, 0, row0, nrows, src, src_pitch_bytes);
     if (row0 + nrows > w->height || src_pitch_bytes < w->row_bytes) return io_fail("write outside the image");
     if (fseeko(w->f, (off_t)(w->data_off + row0 * w->row_bytes), SEEK_SET) != 0) return io_fail("seek failed");
     const uint8_t *p = reinterpret_cast<const uint8_t *>(src);
@@ -307,6 +318,11 @@ extern "C" int sarpro_hip_tiff_row_sink(void *user, size_t row0, size_t nrows, c
 
 extern "C" int sarpro_hip_tiff_finish(sarpro_hip_tiff_writer *w) {
     if (!w) return SARPRO_HIP_ERR_INVALID_ARG;
+    if (w->pyramid) { // the directories went out at creation and the file has its final length: nothing is left but the close
+        const int rc = fclose(w->f) != 0 ? io_fail("close failed") : SARPRO_HIP_OK;
+        delete w;
+        return rc;
+    }
     struct Entry { uint16_t tag, type; uint64_t count; std::vector<uint8_t> data; };
     std::vector<Entry> ents;
     auto add = [&](uint16_t tag, uint16_t type, uint64_t count, const void *data) {
@@ -388,6 +404,256 @@ extern "C" int sarpro_hip_tiff_finish(sarpro_hip_tiff_writer *w) {
     if (fclose(w->f) != 0 && rc == SARPRO_HIP_OK) rc = io_fail("close failed");
     delete w;
     return rc;
+}
+
+// ------------------------------------------------------------------------------------------------
+// tiled writer with overviews, cloud-optimised order: header | every directory with its offset and byte-count arrays,
+// full resolution first | tile data, smallest level first.  Uncompressed, so the whole layout is known at creation: the directories
+// are written then, the file is extended to its final length (tiles never written, and the padding of edge tiles, read as zeros)
+// and rows are scattered into their tiles as they arrive.
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+struct Ifd {
+    struct Entry { uint16_t tag, type; uint64_t count; std::vector<uint8_t> data; };
+    std::vector<Entry> ents;
+    void add(uint16_t tag, uint16_t type, uint64_t count, const void *data) {
+        Entry e{tag, type, count, {}};
+        e.data.assign(reinterpret_cast<const uint8_t *>(data), reinterpret_cast<const uint8_t *>(data) + type_size(type) * count);
+        ents.push_back(std::move(e));
+    }
+    void add_u(uint16_t tag, uint64_t v) { // SHORT where the value fits, as sarpro_hip_tiff_finish writes its scalars
+        if (v <= 0xFFFF) { const uint16_t x = (uint16_t)v; add(tag, tSHORT, 1, &x); }
+        else if (v <= 0xFFFFFFFFull) { const uint32_t x = (uint32_t)v; add(tag, tLONG, 1, &x); }
+        else add(tag, tLONG8, 1, &v);
+    }
+    // the directory and, behind it, the values that do not fit an entry (each padded to 8 bytes)
+    uint64_t bytes(bool big) const {
+        uint64_t n = (big ? 8 : 2) + ents.size() * (big ? 20 : 12) + (big ? 8 : 4);
+        n = (n + 7) & ~7ull;
+        for (const Entry &e : ents)
+            if (e.data.size() > (big ? 8u : 4u)) n += (e.data.size() + 7) & ~7ull;
+        return n;
+    }
+    std::vector<uint8_t> serialize(bool big, uint64_t at, uint64_t next) {
+        std::sort(ents.begin(), ents.end(), [](const Entry &a, const Entry &b) { return a.tag < b.tag; });
+        const size_t esz = big ? 20 : 12, cap = big ? 8 : 4;
+        const uint64_t dir = ((big ? 8 : 2) + ents.size() * esz + (big ? 8 : 4) + 7) & ~7ull;
+        std::vector<uint8_t> out((size_t)dir, 0);
+        size_t q = 0;
+        if (big) { const uint64_t n = ents.size(); std::memcpy(out.data(), &n, 8); q = 8; }
+        else { const uint16_t n = (uint16_t)ents.size(); std::memcpy(out.data(), &n, 2); q = 2; }
+        for (const Entry &e : ents) {
+            const size_t val = q + (big ? 12 : 8);
+            std::memcpy(out.data() + q, &e.tag, 2);
+            std::memcpy(out.data() + q + 2, &e.type, 2);
+            if (big) std::memcpy(out.data() + q + 4, &e.count, 8);
+            else { const uint32_t c = (uint32_t)e.count; std::memcpy(out.data() + q + 4, &c, 4); }
+            if (e.data.size() <= cap) std::memcpy(out.data() + val, e.data.data(), e.data.size());
+            else {
+                const uint64_t where = at + out.size();
+                if (big) std::memcpy(out.data() + val, &where, 8);
+                else { const uint32_t a32 = (uint32_t)where; std::memcpy(out.data() + val, &a32, 4); }
+                out.insert(out.end(), e.data.begin(), e.data.end());
+                while (out.size() & 7) out.push_back(0);
+            }
+            q += esz;
+        }
+        if (big) std::memcpy(out.data() + q, &next, 8);
+        else { const uint32_t n32 = (uint32_t)next; std::memcpy(out.data() + q, &n32, 4); }
+        return out;
+    }
+};
+
+struct PyramidShape {
+    uint64_t width, height, tile;
+    uint32_t samples, bits;
+    int levels;
+};
+
+// level k of the shape: its size and its tile grid
+void pyramid_level(const PyramidShape &s, int k, sarpro_hip_tiff_writer::Level *out) {
+    uint64_t w = s.width, h = s.height;
+    for (int i = 0; i < k; ++i) { w = (w + 1) / 2; h = (h + 1) / 2; }
+    out->w = w; out->h = h;
+    out->tiles_x = (w + s.tile - 1) / s.tile; out->tiles_y = (h + s.tile - 1) / s.tile;
+}
+
+// The directory of level k; `off` (null: zeros, the sizes alone matter) are its tiles' offsets.  Geo tags: directory 0 of `geo`.
+Ifd pyramid_ifd(const PyramidShape &s, int k, bool big, const std::vector<uint64_t> *off, const sarpro_hip_tiff_writer *geo) {
+    sarpro_hip_tiff_writer::Level L;
+    pyramid_level(s, k, &L);
+    const uint64_t ntiles = L.tiles_x * L.tiles_y, tile_bytes = s.tile * s.tile * s.samples * (s.bits / 8);
+    Ifd d;
+    if (k > 0) { const uint32_t reduced = 1; d.add(kNewSubfileType, tLONG, 1, &reduced); }
+    d.add_u(kImageWidth, L.w);
+    d.add_u(kImageLength, L.h);
+    { std::vector<uint16_t> b(s.samples, (uint16_t)s.bits); d.add(kBitsPerSample, tSHORT, s.samples, b.data()); }
+    d.add_u(kCompression, 1);
+    d.add_u(kPhotometric, s.samples >= 3 ? 2 : 1); // RGB | BlackIsZero
+    d.add_u(kSamplesPerPixel, s.samples);
+    d.add_u(kPlanarConfig, 1);
+    d.add_u(kTileWidth, s.tile);
+    d.add_u(kTileLength, s.tile);
+    {
+        std::vector<uint64_t> o(ntiles, 0), len(ntiles, tile_bytes);
+        if (off) o = *off;
+        if (big) { d.add(kTileOffsets, tLONG8, ntiles, o.data()); d.add(kTileByteCounts, tLONG8, ntiles, len.data()); }
+        else {
+            std::vector<uint32_t> o32(o.begin(), o.end()), l32(len.begin(), len.end());
+            d.add(kTileOffsets, tLONG, ntiles, o32.data()); d.add(kTileByteCounts, tLONG, ntiles, l32.data());
+        }
+    }
+    if (s.samples == 2 || s.samples > 3) { std::vector<uint16_t> x(s.samples - (s.samples > 3 ? 3 : 1), 0); d.add(kExtraSamples, tSHORT, x.size(), x.data()); }
+    { std::vector<uint16_t> sf(s.samples, 1); d.add(kSampleFormat, tSHORT, s.samples, sf.data()); }
+    if (k == 0 && geo) {
+        if (geo->has_gt) { // north-up geotransform -> ModelPixelScale + one tiepoint at pixel (0, 0)
+            const double scale[3] = {geo->gt[1], -geo->gt[5], 0.0}, tie[6] = {0, 0, 0, geo->gt[0], geo->gt[3], 0};
+            d.add(kModelPixelScale, tDOUBLE, 3, scale);
+            d.add(kModelTiepoint, tDOUBLE, 6, tie);
+        }
+        if (!geo->geo_keys.empty()) d.add(kGeoKeyDirectory, tSHORT, geo->geo_keys.size(), geo->geo_keys.data());
+        if (!geo->geo_doubles.empty()) d.add(kGeoDoubleParams, tDOUBLE, geo->geo_doubles.size(), geo->geo_doubles.data());
+        if (!geo->geo_ascii.empty()) d.add(kGeoAsciiParams, tASCII, geo->geo_ascii.size(), geo->geo_ascii.data());
+    }
+    return d;
+}
+
+// where everything lies: ifd_off[k] and data_off[k] of levels 0..levels; returns the file's size
+uint64_t pyramid_layout(const PyramidShape &s, bool big, const sarpro_hip_tiff_writer *geo, std::vector<uint64_t> *ifd_off, std::vector<uint64_t> *data_off) {
+    uint64_t pos = big ? 16 : 8;
+    ifd_off->assign((size_t)s.levels + 1, 0);
+    data_off->assign((size_t)s.levels + 1, 0);
+    for (int k = 0; k <= s.levels; ++k) {
+        (*ifd_off)[k] = pos;
+        pos += pyramid_ifd(s, k, big, nullptr, geo).bytes(big);
+    }
+    pos = (pos + 15) & ~15ull;
+    const uint64_t tile_bytes = s.tile * s.tile * s.samples * (s.bits / 8);
+    for (int k = s.levels; k >= 0; --k) { // the smallest level first
+        sarpro_hip_tiff_writer::Level L;
+        pyramid_level(s, k, &L);
+        (*data_off)[k] = pos;
+        pos += L.tiles_x * L.tiles_y * tile_bytes;
+    }
+    return pos;
+}
+
+bool pyramid_shape(uint64_t width, uint64_t height, uint32_t samples, uint32_t bits, uint32_t tile, int levels, PyramidShape *s) {
+    if (!width || !height || width > 0x7FFFFFFFull || height > 0x7FFFFFFFull || !samples || samples > 64 || (bits != 8 && bits != 16)) return false;
+    if (tile % 16 || tile > 65536 || levels < 0 || levels > SARPRO_HIP_OVR_MAX_LEVELS) return false;
+    *s = PyramidShape{width, height, tile ? tile : 512u, samples, bits, levels};
+    return true;
+}
+
+// the strip writer's rule on the whole file: classic while the file and a 1 MiB reserve stay below 2^32 - 1
+bool pyramid_big(uint64_t classic_bytes) { return classic_bytes + (1u << 20) >= 0xFFFFFFFFull; }
+
+// SARPRO_HIP_TIFF_BIGTIFF=YES (or 1) in the environment when a pyramid file is created: BigTIFF whatever the size, as GDAL's BIGTIFF=YES
+// creation option (a reader that wants one form for every product; the suite checks the BigTIFF form on small files with it)
+bool pyramid_big_requested() {
+    const char *e = getenv("SARPRO_HIP_TIFF_BIGTIFF");
+    return e && (!strcmp(e, "1") || !strcmp(e, "YES") || !strcmp(e, "yes"));
+}
+
+// closes the file and frees the writer unless it is released to the caller
+struct WriterCloser {
+    void operator()(sarpro_hip_tiff_writer *w) const {
+        if (w->f) fclose(w->f);
+        delete w;
+    }
+};
+
+} // namespace
+
+extern "C" int sarpro_hip_tiff_pyramid_is_bigtiff(uint64_t width, uint64_t height, uint32_t samples, uint32_t bits, uint32_t tile, int levels,
+                                                  uint64_t *file_bytes_out) {
+    PyramidShape s;
+    if (!pyramid_shape(width, height, samples, bits, tile, levels, &s)) return SARPRO_HIP_ERR_INVALID_ARG;
+    try {
+        std::vector<uint64_t> io, dof;
+        uint64_t total = pyramid_layout(s, false, nullptr, &io, &dof);
+        const bool big = pyramid_big(total);
+        if (big) total = pyramid_layout(s, true, nullptr, &io, &dof);
+        if (file_bytes_out) *file_bytes_out = total;
+        return big ? 1 : 0;
+    } catch (...) { return SARPRO_HIP_ERR_OOM; } // nothing may unwind across the C ABI
+}
+
+static int tiff_create_pyramid_impl(const char *path, const PyramidShape &s, const double *geotransform6, const sarpro_hip_tiff *geo_keys_from,
+                                    sarpro_hip_tiff_writer **out) {
+    std::unique_ptr<sarpro_hip_tiff_writer, WriterCloser> owner(new sarpro_hip_tiff_writer()); // (an exception or an early return frees it)
+    sarpro_hip_tiff_writer *w = owner.get();
+    w->width = s.width; w->height = s.height; w->samples = s.samples; w->bits = s.bits;
+    w->row_bytes = s.width * s.samples * (s.bits / 8);
+    w->pyramid = true; w->tile = s.tile; w->tile_bytes = s.tile * s.tile * s.samples * (s.bits / 8);
+    if (geotransform6) { w->has_gt = true; std::memcpy(w->gt, geotransform6, sizeof(w->gt)); }
+    if (geo_keys_from) { w->geo_keys = geo_keys_from->geo_keys; w->geo_doubles = geo_keys_from->geo_doubles; w->geo_ascii = geo_keys_from->geo_ascii; }
+    std::vector<uint64_t> ifd_off, data_off;
+    {   // the rule is taken without the geo tags (sarpro_hip_tiff_pyramid_is_bigtiff answers for a shape); they live off the reserve
+        std::vector<uint64_t> io, dof;
+        w->big = pyramid_big(pyramid_layout(s, false, nullptr, &io, &dof)) || pyramid_big_requested();
+    }
+    const uint64_t total = pyramid_layout(s, w->big, w, &ifd_off, &data_off);
+    if (!w->big && total > 0xFFFFFFFFull) return io_fail("classic TIFF overflow");
+    w->lev.resize((size_t)s.levels + 1);
+    for (int k = 0; k <= s.levels; ++k) { pyramid_level(s, k, &w->lev[k]); w->lev[k].data_off = data_off[k]; }
+    FILE *f = fopen(path, "wb");
+    if (!f) return io_fail(std::string("cannot create ") + path);
+    w->f = f;
+    uint8_t hdr[16] = {0};
+    hdr[0] = hdr[1] = host_is_big_endian() ? 'M' : 'I';
+    const uint16_t magic = w->big ? 43 : 42;
+    std::memcpy(hdr + 2, &magic, 2);
+    if (w->big) { const uint16_t eight = 8; std::memcpy(hdr + 4, &eight, 2); std::memcpy(hdr + 8, &ifd_off[0], 8); }
+    else { const uint32_t o32 = (uint32_t)ifd_off[0]; std::memcpy(hdr + 4, &o32, 4); }
+    if (fwrite(hdr, 1, w->big ? 16 : 8, f) != (w->big ? 16u : 8u)) return io_fail("write failed");
+    for (int k = 0; k <= s.levels; ++k) {
+        const sarpro_hip_tiff_writer::Level &L = w->lev[k];
+        std::vector<uint64_t> off(L.tiles_x * L.tiles_y);
+        for (size_t i = 0; i < off.size(); ++i) off[i] = L.data_off + i * w->tile_bytes;
+        const std::vector<uint8_t> dir = pyramid_ifd(s, k, w->big, &off, w).serialize(w->big, ifd_off[k], k < s.levels ? ifd_off[k + 1] : 0);
+        if (fseeko(f, (off_t)ifd_off[k], SEEK_SET) != 0 || fwrite(dir.data(), 1, dir.size(), f) != dir.size()) return io_fail("write failed");
+    }
+    if (fflush(f) != 0 || ftruncate(fileno(f), (off_t)total) != 0) return io_fail("cannot extend the file to its final length");
+    *out = owner.release();
+    return SARPRO_HIP_OK;
+}
+
+extern "C" int sarpro_hip_tiff_create_pyramid(const char *path, uint64_t width, uint64_t height, uint32_t samples, uint32_t bits, uint32_t tile, int levels,
+                                              const double *geotransform6, const sarpro_hip_tiff *geo_keys_from, sarpro_hip_tiff_writer **out) {
+    if (!path || !out) return SARPRO_HIP_ERR_INVALID_ARG;
+    *out = nullptr;
+    PyramidShape s;
+    if (!pyramid_shape(width, height, samples, bits, tile, levels, &s)) return SARPRO_HIP_ERR_INVALID_ARG;
+    try { return tiff_create_pyramid_impl(path, s, geotransform6, geo_keys_from, out); }
+    catch (...) { *out = nullptr; return io_fail("out of memory while laying out the tiled TIFF"); } // never unwind across the C ABI
+}
+
+static int tiff_write_level_rows_impl(sarpro_hip_tiff_writer *w, int level, size_t row0, size_t nrows, const void *src, size_t src_pitch_bytes) {
+    const sarpro_hip_tiff_writer::Level &L = w->lev[(size_t)level];
+    const uint64_t px = (uint64_t)w->samples * (w->bits / 8), row_bytes = L.w * px, tile_row = w->tile * px;
+    if (row0 > L.h || nrows > L.h - row0 || src_pitch_bytes < row_bytes) return io_fail("write outside the image");
+    const uint8_t *p = reinterpret_cast<const uint8_t *>(src);
+    for (uint64_t r = row0; r < row0 + nrows;) { // the rows that fall into one row of tiles: per tile one contiguous piece of the file
+        const uint64_t tr = r / w->tile, in_t = r - tr * w->tile, take = std::min<uint64_t>(w->tile - in_t, row0 + nrows - r);
+        for (uint64_t tc = 0; tc < L.tiles_x; ++tc) {
+            const uint64_t wb = std::min<uint64_t>(w->tile, L.w - tc * w->tile) * px;
+            w->scratch.assign((size_t)(take * tile_row), 0); // (the padding of an edge tile's rows: zeros)
+            for (uint64_t k = 0; k < take; ++k) std::memcpy(w->scratch.data() + k * tile_row, p + (r - row0 + k) * src_pitch_bytes + tc * tile_row, (size_t)wb);
+            const uint64_t at = L.data_off + (tr * L.tiles_x + tc) * w->tile_bytes + in_t * tile_row;
+            if (fseeko(w->f, (off_t)at, SEEK_SET) != 0) return io_fail("seek failed");
+            if (fwrite(w->scratch.data(), 1, w->scratch.size(), w->f) != w->scratch.size()) return io_fail("write failed");
+        }
+        r += take;
+    }
+    return SARPRO_HIP_OK;
+}
+
+extern "C" int sarpro_hip_tiff_write_level_rows(sarpro_hip_tiff_writer *w, int level, size_t row0, size_t nrows, const void *src, size_t src_pitch_bytes) {
+    if (!w || !src || !w->pyramid || level < 0 || (size_t)level >= w->lev.size()) return SARPRO_HIP_ERR_INVALID_ARG;
+    try { return tiff_write_level_rows_impl(w, level, row0, nrows, src, src_pitch_bytes); }
+    catch (...) { return io_fail("out of memory while writing rows"); }
 }
 
 // save.rs:71-81: the geotransform of a resized / padded product
