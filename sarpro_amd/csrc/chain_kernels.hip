@@ -568,9 +568,13 @@ __global__ __launch_bounds__(kStatsBlock) void k_chain_finish(ChainFinishArgs a)
 // ------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kStatsBlock) void k_chain_predict(ChainPredictArgs a) {
     // The second launch (behind a fused pass): only after an undercut lowest level whose true value the pass recorded, on a chain that
-    // has not had its second pass yet (nothing this kernel writes is read by this test -- `retried` is the retry kernel's).
-    if (a.second && !(a.spec->spec_ok == kSpecRescaled && a.spec->verdict == 1u && !a.spec->pool_overflow && a.spec->retry_min == 1u &&
-                      !a.spec->retried && !(a.spec->force & kSpecForceNoRetry))) return;
+    // has not had its second pass yet.  The 64 blocks of this launch must all decide the same, whenever they are dispatched, so the
+    // test reads only what no block of the launch changes: retry_min (set with the verdict of the rescaled form only, cleared by the
+    // FIRST launch only), `retried` (the retry kernel's, or k_spec_verdict's), and verdict / pool_overflow / force, which block 0
+    // rewrites with the values they must hold to get here (1, 0, a.force).  NOT spec_ok: block 0 rewrites it below, and on a
+    // Rescaled -> Identity retry a block dispatched after that would return without rebuilding its slice of the blue table.
+    if (a.second && !(a.spec->retry_min == 1u && !a.spec->retried && a.spec->verdict == 1u && !a.spec->pool_overflow &&
+                      !(a.spec->force & kSpecForceNoRetry))) return;
     __shared__ double est[2][256], fin[2][256]; // per band: estimated pixels per level, per FINAL level (after the predicted rescale)
     __shared__ uint8_t resc[2][256];
     __shared__ int s_ok[2], s_fwc, s_f;

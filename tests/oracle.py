@@ -108,6 +108,21 @@ def pipeline(x: np.ndarray, bit_depth: int, strategy: int, want_stats: bool = Fa
     return (rc, out, s) if want_stats else (rc, out)
 
 
+def clahe_levels_u8(x: np.ndarray, strategy: int) -> np.ndarray:
+    """One band's u8 levels BEFORE the u8 rescale: autoscale_db_image_advanced at BitDepth::U8 (autoscale.rs:452-659), i.e. what
+    pipeline() computes minus its last step scale_u16_to_u8 (autoscale.rs:670).  The lowest of these levels is what the speculative
+    chain proves or predicts (k_chain_predict)."""
+    x = np.ascontiguousarray(x, np.float32)
+    rows, cols = x.shape
+    db, mask = db_mask(x)
+    v = np.empty((rows, cols), np.uint16)
+    s = Stats()
+    rc = lib().sarpro_oracle_autoscale_db_image_advanced(_p(db), _p(mask), C.c_size_t(rows), C.c_size_t(cols), 0, int(strategy),
+                                                         _p(v), C.byref(s))
+    assert rc == OK, rc
+    return v
+
+
 def tamed_synrgb_u8(x: np.ndarray, is_copol: bool) -> np.ndarray:
     x = np.ascontiguousarray(x, np.float32)
     db, mask = db_mask(x)

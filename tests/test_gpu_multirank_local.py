@@ -11,6 +11,7 @@ import pytest
 import f32data
 import oracle
 import sarpro_amd as S
+import undercutscenes as U
 from sarpro_amd import AutoscaleStrategy as St, BitDepth as Bd, PolarizationOperation as Op, SyntheticRgbMode as Mode, synth
 
 pytestmark = pytest.mark.gpu
@@ -165,6 +166,47 @@ def test_row_stripes_take_the_fused_clahe_rgb_route(ranks, force):
         lv = np.concatenate([u[0].ravel(), u[1].ravel()])
         f = key[0][2]
         assert key[0][3][0] == int((lv < f).sum()) and (f == 37 or key[0][3][1] == int((lv <= f).sum()))
+
+
+@pytest.mark.parametrize("case", ["to_zero_proven", "to_nonzero"])
+@pytest.mark.parametrize("ranks", [2, 8, "ragged+empty"])
+def test_row_stripes_second_chance_on_a_natural_undercut(ranks, case):
+    """A lowest level that occurs only off the sampled rows (tests/undercutscenes.py, no SPEC_FORCE), and in some ranks' stripes only:
+    the true lowest level is not the pass's atomicMin here but the lowest occupied bin of the ranks' SUMMED below_hist
+    (k_spec_verdict), so every rank -- also one whose stripe holds no such pixel, or no row at all -- runs the second prediction
+    and the second pass on the same level.  "to_zero_proven": Rescaled -> Identity; "to_nonzero": min_pred[0] 2 -> 1."""
+    rows, cols, pitch = 403, 520, 576
+    b = list(U.scene(case, (rows, cols)))
+    facts = [U.facts(x, U.STRIDE) for x in b]
+    rc, ref, _, _ = oracle.dualpol_synrgb(b[0].astype(np.float32), b[1].astype(np.float32), int(St.Clahe))
+    assert rc == 0
+    splits = SPLITS[ranks] or list(zip(*S.host_stripe_plan(rows, ranks)))
+    holds = [bool(((facts[0]["below_rows"] >= r0) & (facts[0]["below_rows"] < r0 + nr)).any()) for r0, nr in splits]
+    assert any(holds) and not all(holds), holds  # some ranks learn of the undercut through the all-reduce only
+    d = [[to_dev(x[r0:r0 + nr], pitch, torch.int16) for x in b] for r0, nr in splits]
+    rgb = [torch.zeros((max(nr, 1), pitch * 3), dtype=torch.uint8, device="cuda") for _, nr in splits]
+    reports = [None] * len(splits)
+
+    def body(c, k, r0, nr):
+        st = c.stripe_run_u16(d[k][0].data_ptr(), d[k][1].data_ptr(), rows, cols, r0, nr, pitch, St.Clahe, Mode.Default, rgb[k].data_ptr(), pitch)
+        reports[k] = c.spec_report()
+        return st
+    _, names = run_ranks(splits, body, {"SAMPLED_HIST_MIN_PX": 0, "SAMPLE_STRIDE": U.STRIDE})
+    print("\nstripes undercut", case, ranks, holds, {k: reports[0][k] for k in ("spec_ok", "verdict", "retried", "min_pred", "floor_pred", "floor_first", "n_below_min", "n_lt", "target")})
+    got = np.concatenate([t.cpu().numpy().reshape(-1, pitch, 3)[:nr, :cols] for t, (_, nr) in zip(rgb, splits)], axis=0)
+    assert np.array_equal(got, ref), (ranks, case, reports[0], int((got != ref).sum()))
+    key = [(r["spec_ok"], r["verdict"], r["floor_pred"], tuple(r["n_lt"]), r["target"], r["n_below_min"], tuple(r["min_pred"]), r["retried"], r["floor_first"]) for r in reports]
+    assert all(k == key[0] for k in key), key
+    rep = reports[0]
+    want = [facts[0]["true_min"], 0 if case == "to_zero_proven" else facts[1]["true_min"]]
+    assert (want[0] == 0) == (case == "to_zero_proven") and (want[1] == 0) == (case == "to_zero_proven"), want
+    assert rep["retried"] == 1 and rep["min_pred"] == want and rep["spec_ok"] == (1 if want == [0, 0] else 2) and rep["n_below_min"] == 0, (rep, want)
+    assert all("allreduce_spec_counts_retry" in nm and "clahe_rgb_fused_retry" in nm for nm in names), names
+    assert rep["verdict"] == 0, rep
+    u = [oracle.pipeline(x.astype(np.float32), 0, int(St.Clahe))[1] for x in b]  # the oracle's FINAL levels
+    lv = np.concatenate([u[0].ravel(), u[1].ravel()])
+    f = rep["floor_pred"]
+    assert rep["n_lt"][0] == int((lv < f).sum()) and (f == 37 or rep["n_lt"][1] == int((lv <= f).sum())), rep
 
 
 @pytest.mark.parametrize("strategy", [St.Clahe, St.Robust])

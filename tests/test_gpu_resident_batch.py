@@ -9,10 +9,12 @@ import torch
 
 import oracle
 import sarpro_amd as S
+import undercutscenes as U
 from sarpro_amd import AutoscaleStrategy as St, SyntheticRgbMode as Mode
 from sarpro_amd import synth
 
 pytestmark = pytest.mark.gpu
+NEIGHBOUR_SEEDS = (0, 1, 2, 3, 4, 5)  # offsets to synth.SEED_SCENE_A: natural scenes whose predicted floor stands at 264 x 520 (their route alone: accepted)
 
 
 def make_scenes(rows, cols, pitch, defs):
@@ -86,6 +88,42 @@ def test_resident_batch_forced_refutation_in_the_middle(force, route, monkeypatc
     assert rep["processed"] == len(defs) and route in routes and "n/a" not in routes, routes
     for i in range(len(defs)):
         assert np.array_equal(rgb_of(outs[i], rows, cols, pitch), oracle_rgb(host[i], St.Clahe))
+
+
+@pytest.mark.parametrize("lanes", [1, 3])
+def test_resident_batch_natural_undercut_in_the_middle(lanes, monkeypatch):
+    """No force: a scene whose lowest level occurs only off the sampled rows (tests/undercutscenes.py, "to_zero_proven": the second
+    k_chain_predict launch takes the chain from the rescaled form to the identity form) between ordinary scenes, the cycle run twice.
+    The second prediction's 64 blocks and the retry pass share the chip with the other lanes' sweeps here: the planted scene must come
+    out `retried` with the oracle's raster -- every slice of its blue table rebuilt -- and its neighbours `accepted`, untouched."""
+    rows, cols = 264, 520
+    pitch = (cols + 63) // 64 * 64
+    monkeypatch.setenv("SARPRO_HIP_SAMPLED_HIST_MIN_PX", "0")
+    monkeypatch.setenv("SARPRO_HIP_SAMPLE_STRIDE", str(U.STRIDE))
+    host = [[synth.scene_u16(rows, cols, b, seed=synth.SEED_SCENE_A + k) for b in range(2)] for k in NEIGHBOUR_SEEDS]
+    mid = len(host) // 2
+    host.insert(mid, list(U.scene("to_zero_proven", (rows, cols))))
+    host = host + host
+    dev = []
+    for hb in host:
+        db = []
+        for b in range(2):
+            t = torch.zeros((rows, pitch), dtype=torch.int16, device="cuda")
+            t[:, :cols] = torch.from_numpy(hb[b].view(np.int16)).cuda()
+            db.append(t)
+        dev.append(db)
+    refs = [oracle_rgb(h, St.Clahe) for h in host[: len(host) // 2]] * 2
+    outs = [torch.zeros((rows, pitch * 3), dtype=torch.uint8, device="cuda") for _ in host]
+    with S.Context(0) as c:
+        batch = [(d[0].data_ptr(), d[1].data_ptr(), o.data_ptr()) for d, o in zip(dev, outs)]
+        rep, st, routes = c.dev_batch_dualpol_synrgb_u16(batch, rows, cols, pitch, St.Clahe, Mode.Default, pitch, lanes=lanes)
+    print("\nbatch undercut", lanes, routes)
+    assert rep == {"processed": len(host), "skipped": 0, "errors": 0, "rc": 0} and not any(st)
+    for i in range(len(host)):
+        got = rgb_of(outs[i], rows, cols, pitch)
+        assert np.array_equal(got, refs[i]), (i, routes[i], int((got != refs[i]).sum()))
+    n = len(host) // 2
+    assert routes == (["accepted"] * mid + ["retried"] + ["accepted"] * (n - 1 - mid)) * 2, routes
 
 
 @pytest.mark.parametrize("strategy", [St.Robust, St.Tamed, St.Standard])

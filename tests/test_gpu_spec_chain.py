@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import oracle
+import undercutscenes as U
 from sarpro_amd import AutoscaleStrategy as St, SyntheticRgbMode as Mode
 from sarpro_amd import synth
 import sarpro_amd as S
@@ -446,3 +447,99 @@ def test_fused_rgb_pass_wide_windows_take_the_byte_table_form(kind, monkeypatch)
                 f = rep["floor_pred"]
                 lv = np.concatenate([r1.ravel(), r2.ravel()])
                 assert rep["n_lt"][0] == int((lv < f).sum()) and (f == 37 or rep["n_lt"][1] == int((lv <= f).sum()))
+
+
+# ---------------------------------------------------------------------------- a lowest level that occurs only OFF the sampled rows
+# (tests/undercutscenes.py; tests/test_undercut_scenes.py pins on the CPU that every scene is on its case).  No SPEC_FORCE: the level
+# the pass records below the prediction differs from the sampled one, min_pred changes between the passes and spec_ok may too.
+def _check_undercut_report(case, rep, facts, finals):
+    """The report the device must give for a scene of `case`; facts = undercutscenes.facts per band, finals = the oracle's FINAL levels."""
+    kinds = U.KINDS[case]
+    if "untracked" in kinds:  # a prediction above 127 has no record: min_known is false whatever the other band recorded, the exact kernels run
+        k = kinds.index("untracked")
+        assert rep["spec_ok"] == 2 and rep["min_pred"][k] > 127, rep  # (the scene IS on the rescaled form with an untracked band)
+        assert rep["verdict"] == 1 and rep["retried"] == 0 and rep["n_below_min"] > 0, rep
+        return
+    want = [0 if kind == "proven" else f["true_min"] for kind, f in zip(kinds, facts)]  # the second pass runs on the TRUE lowest levels
+    assert rep["retried"] == 1 and rep["min_pred"] == want and rep["n_below_min"] == 0, (rep, want)
+    assert rep["spec_ok"] == (1 if want == [0, 0] else 2), (rep, want)
+    for kind, m in zip(kinds, want):
+        assert (m > 0) == (kind in ("nonzero", "plain")), (kinds, want)
+    assert rep["verdict"] == 0 and rep["outcome"] == "retried", rep
+    f = rep["floor_pred"]
+    lv = np.concatenate([x.ravel() for x in finals])
+    assert rep["n_lt"][0] == int((lv < f).sum()) and (f == 37 or rep["n_lt"][1] == int((lv <= f).sum())), rep
+    assert f == 37 or rep["n_lt"][0] < rep["target"] <= rep["n_lt"][1], rep
+
+
+@pytest.mark.parametrize("shape", [(264, 520), (1000, 777)])
+@pytest.mark.parametrize("case", U.CASES)
+def test_fused_rgb_pass_second_chance_on_a_natural_undercut(case, shape, monkeypatch):
+    """The fused pass finds level bytes below the predicted lowest level of a band, records the lowest of them, k_chain_predict runs again
+    on that level and the retry kernel recomposes: Rescaled -> Identity when the true minimum is 0 and the other band holds level 0
+    (the retry kernel's identity body behind a first pass in the rescaled body; tables, thresholds, identity_out and resc_out rebuilt
+    for another rescale), Rescaled -> Rescaled with another min_pred otherwise.  A band whose prediction lies above 127 is not tracked:
+    the exact kernels.  Then the un-planted twin and the planted scene again on the same context: nothing of the retry leaks."""
+    monkeypatch.setenv("SARPRO_HIP_SAMPLED_HIST_MIN_PX", "0")
+    monkeypatch.setenv("SARPRO_HIP_SAMPLE_STRIDE", str(U.STRIDE))
+    b1, b2 = U.scene(case, shape)
+    t1, t2 = U.scene(case, shape, planted=False)
+    facts = [U.facts(b, U.STRIDE) for b in (b1, b2)]
+    rrgb, r1, r2 = ref(b1, b2)
+    trgb, _, _ = ref(t1, t2)
+    with S.Context(0, timing=True) as c:
+        rgb, names = run_rgb_only(c, b1, b2)
+        rep = c.spec_report()
+        print("\nundercut", case, shape, {k: rep[k] for k in ("spec_ok", "verdict", "retried", "min_pred", "floor_pred", "floor_first", "n_below_min", "n_lt", "target")})
+        assert "clahe_rgb_fused" in names and "clahe_rgb_fused_retry" in names, names
+        assert np.array_equal(rgb, rrgb), (case, rep, int((rgb != rrgb).sum()))
+        _check_undercut_report(case, rep, facts, (r1, r2))
+        rgb, _ = run_rgb_only(c, t1, t2)
+        rept = c.spec_report()
+        assert np.array_equal(rgb, trgb), (case, rept, int((rgb != trgb).sum()))
+        rgb, _ = run_rgb_only(c, b1, b2)
+        rep2 = c.spec_report()
+        assert np.array_equal(rgb, rrgb), (case, rep2, int((rgb != rrgb).sum()))
+        _check_undercut_report(case, rep2, facts, (r1, r2))
+        assert all(rep2[k] == rep[k] for k in ("spec_ok", "verdict", "retried", "min_pred", "floor_pred", "floor_first", "n_lt", "n_below_min")), (rep, rep2)
+
+
+def test_fused_rgb_pass_natural_undercut_without_the_second_chance(monkeypatch):
+    """SPEC_FORCE = noretry on the Rescaled -> Identity scene: the undercut refutes, no second prediction, the exact kernels."""
+    monkeypatch.setenv("SARPRO_HIP_SAMPLED_HIST_MIN_PX", "0")
+    monkeypatch.setenv("SARPRO_HIP_SAMPLE_STRIDE", str(U.STRIDE))
+    monkeypatch.setenv("SARPRO_HIP_SPEC_FORCE", "noretry")
+    b1, b2 = U.scene("to_zero_proven", (264, 520))
+    rrgb, _, _ = ref(b1, b2)
+    with S.Context(0, timing=True) as c:
+        rgb, names = run_rgb_only(c, b1, b2)
+        rep = c.spec_report()
+        print("\nundercut noretry", rep)
+        assert "clahe_rgb_fused" in names and np.array_equal(rgb, rrgb), rep
+        assert rep["verdict"] == 1 and rep["retried"] == 0 and rep["spec_ok"] == 2 and rep["n_below_min"] > 0 and rep["min_pred"][0] > 0, rep
+
+
+def test_fused_rgb_pass_natural_undercut_with_a_wrong_floor(monkeypatch):
+    """SPEC_FORCE = mispredict on the Rescaled -> Identity scene: an undercut and a floor that is one too high coincide.  The undercut
+    decides the first verdict (retry_floor stays -1: k_chain_repredict returns), the second k_chain_predict launch shifts its floor by
+    one as well and the one second pass runs on it.  Two endings are legal: the shifted floor is refuted (verdict 1, retried 1: the
+    exact kernels produced the raster), or the sample's estimate was one too low and the shift made it right (verdict 0, retried 1,
+    the oracle's counts).  Either way the second pass ran on the true lowest levels, and the raster is the oracle's.
+    Observed on an MI355X: the first ending -- floor_first 2, the second pass on floor 3 refuted (n_lt = [22283, 22296] above the target
+    13728), verdict 1, retried 1, spec_ok 1, min_pred [0, 0]."""
+    monkeypatch.setenv("SARPRO_HIP_SAMPLED_HIST_MIN_PX", "0")
+    monkeypatch.setenv("SARPRO_HIP_SAMPLE_STRIDE", str(U.STRIDE))
+    monkeypatch.setenv("SARPRO_HIP_SPEC_FORCE", "mispredict")
+    b1, b2 = U.scene("to_zero_proven", (264, 520))
+    rrgb, r1, r2 = ref(b1, b2)
+    with S.Context(0, timing=True) as c:
+        rgb, names = run_rgb_only(c, b1, b2)
+        rep = c.spec_report()
+        print("\nundercut mispredict", rep)
+        assert "clahe_rgb_fused" in names and np.array_equal(rgb, rrgb), rep
+        assert rep["retried"] == 1 and rep["spec_ok"] == 1 and rep["min_pred"] == [0, 0] and rep["n_below_min"] == 0, rep
+        assert rep["verdict"] in (0, 1), rep
+        if rep["verdict"] == 0:
+            f = rep["floor_pred"]
+            lv = np.concatenate([r1.ravel(), r2.ravel()])
+            assert rep["n_lt"][0] == int((lv < f).sum()) and (f == 37 or rep["n_lt"][1] == int((lv <= f).sum())), rep
