@@ -3,11 +3,7 @@
 // entry point replaces.  No CPU fallback exists anywhere in this file: every raster result is
 // produced by the kernels in kernels.hip.
 #include <algorithm>
-#include <chrono>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <future>
 #include <string>
 
 #include "api_common.h"
@@ -57,7 +53,7 @@ int bands_u8_table_dev(sarpro_hip_ctx *ctx, const uint16_t *const d_in[], int nb
     if (rc == kRerunOnHostRoute) return SARPRO_HIP_OK;
     RETCHK(rc);
     for (int b = 0; b < nb; ++b) {
-        out[b].lut = ctx->luts.as<uint8_t>() + (size_t)b * 131072;
+        out[b].lut = layout::lut_of(ctx, b);
         out[b].dev_state = reinterpret_cast<const ChainBandState *>(ctx->chain_state.as<uint8_t>());
         out[b].lut_cap = (ctx->chain_levels_cap + 15u) & ~15u;
     }
@@ -145,10 +141,10 @@ int sarpro::synrgb_flat_dev(sarpro_hip_ctx *ctx, int mode, int strategy, const u
     const size_t W = 4096;
     const size_t full_rows = n / W, tail = n - full_rows * W;
     const bool suppressed = strategy == SARPRO_STRATEGY_TAMED || strategy == SARPRO_STRATEGY_CLAHE;
-    std::vector<uint8_t> luts(66048), tables(66048);
-    int fwc = -1;
+    std::vector<uint8_t> tables(layout::kComposeBytes);
+    uint64_t h[256] = {};
     if (suppressed) {
-        HIPCHK(ctx, ctx->level_hist.reserve(sizeof(uint64_t) * 256 * kMaxBands));
+        HIPCHK(ctx, layout::reserve_level_hist(ctx));
         HIPCHK(ctx, hipMemsetAsync(ctx->level_hist.p, 0, sizeof(uint64_t) * 256, ctx->stream));
         for (const uint8_t *p : {d_b1, d_b2}) {
             KernelTimer t(ctx, "hist256_u8");
@@ -156,21 +152,15 @@ int sarpro::synrgb_flat_dev(sarpro_hip_ctx *ctx, int mode, int strategy, const u
             if (tail) HIPCHK(ctx, launch_hist256_u8(p + full_rows * W, W, 1, (uint32_t)tail, ctx->level_hist.as<unsigned long long>(), ctx->stream));
         }
         if (reduce) RETCHK(comm_allreduce_sum_u64_async(ctx, ctx->level_hist.as<uint64_t>(), 256));
-        uint64_t h[256];
         HIPCHK(ctx, hipMemcpyAsync(h, ctx->level_hist.p, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        fwc = synrgb_floor_from_hist(h, n_total);
-        synrgb_luts_suppressed(fwc, luts.data());
-    } else {
-        synrgb_luts_default(luts.data());
     }
-    uint8_t ident[256];
-    for (int i = 0; i < 256; ++i) ident[i] = (uint8_t)i;
-    fold_compose_tables(luts.data(), fwc, ident, ident, tables.data());
-    HIPCHK(ctx, ctx->tables.reserve(66048 + 512));
-    HIPCHK(ctx, ctx->h_upload.reserve(2 * 131072 + 2 * 64 * 256 * 8 + 66048 + 1024));
-    std::memcpy(ctx->h_upload.p, tables.data(), 66048); // pinned and the context's own: the copy needs no wait of its own
-    HIPCHK(ctx, hipMemcpyAsync(ctx->tables.p, ctx->h_upload.p, 66048, hipMemcpyHostToDevice, ctx->stream));
+    build_compose_tables(strategy, h, n_total, nullptr, nullptr, tables.data());
+    HIPCHK(ctx, layout::reserve_tables(ctx));
+    HIPCHK(ctx, layout::reserve_h_upload(ctx));
+    uint8_t *tstage = ctx->h_upload.as<uint8_t>() + layout::kUploadOffFlatTables;
+    std::memcpy(tstage, tables.data(), layout::kComposeBytes); // pinned and the context's own: the copy needs no wait of its own
+    HIPCHK(ctx, hipMemcpyAsync(ctx->tables.p, tstage, layout::kComposeBytes, hipMemcpyHostToDevice, ctx->stream));
     const bool al = ptr_aligned16(d_b1) && ptr_aligned16(d_b2) && ptr_aligned16(d_rgb);
     ComposeArgs c{};
     c.tables = ctx->tables.as<uint8_t>();
@@ -521,7 +511,7 @@ extern "C" int sarpro_hip_stripe_phase2(sarpro_hip_stripe *s, uint64_t **d_buf, 
     RETCHK(job_after_phase1(s->job));
     RETCHK(job_phase2(s->job));
     HIPCHK(s->job.ctx, hipStreamSynchronize(s->job.ctx->stream));
-    if (s->job.clahe()) { *d_buf = s->job.ctx->tile_bins.as<uint64_t>(); *count = 64 * 256 * 2; }
+    if (s->job.clahe()) { *d_buf = s->job.ctx->tile_bins.as<uint64_t>(); *count = layout::kTileBinCount * kMaxBands; }
     else { *d_buf = nullptr; *count = 0; }
     s->phase = 2;
     return SARPRO_HIP_OK;
@@ -532,7 +522,7 @@ extern "C" int sarpro_hip_stripe_phase3(sarpro_hip_stripe *s, uint64_t **d_buf, 
     void *outs[kMaxBands] = {nullptr, nullptr};
     RETCHK(job_phase3(s->job, outs, 0));
     HIPCHK(s->job.ctx, hipStreamSynchronize(s->job.ctx->stream));
-    if (s->job.clahe()) { *d_buf = s->job.ctx->level_hist.as<uint64_t>(); *count = 256 * 2; }
+    if (s->job.clahe()) { *d_buf = s->job.ctx->level_hist.as<uint64_t>(); *count = layout::kLevelHistCount * kMaxBands; }
     else { *d_buf = nullptr; *count = 0; } // percentile strategies: level histogram follows from the reduced DN histogram
     s->phase = 3;
     return SARPRO_HIP_OK;

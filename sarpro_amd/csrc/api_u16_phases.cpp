@@ -1,12 +1,8 @@
 // api_u16_phases.cpp -- the u16 flavour as explicit phases: the host route (statistics and tables on the host between the passes) and the
 // row-stripe protocol's steps (each phase ends in a small integer reduction).
 #include <algorithm>
-#include <chrono>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <future>
-#include <string>
 
 #include "api_common.h"
 #include "chain_kernels.h"
@@ -137,8 +133,8 @@ int job_after_phase1(U16Job &J) {
     HIPCHK(ctx, ctx->h_ghist.reserve(sizeof(uint64_t) * 65536 * kMaxBands));
     HIPCHK(ctx, hipMemcpyAsync(ctx->h_ghist.p, ctx->ghist.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    HIPCHK(ctx, ctx->luts.reserve(2 * 131072));
-    HIPCHK(ctx, ctx->h_upload.reserve(2 * 131072 + 2 * 64 * 256 * 8 + 66048 + 1024));
+    HIPCHK(ctx, layout::reserve_luts(ctx));
+    HIPCHK(ctx, layout::reserve_h_upload(ctx));
     // the bands are independent: band 1 is worked on by a helper thread while this thread does band 0
     auto band_work = [&J, ctx](int b) -> int {
         uint64_t *h = ctx->h_ghist.as<uint64_t>() + (size_t)b * 65536;
@@ -191,15 +187,15 @@ void job_rescale_from_level_hist(U16Job &J, int b) {
 int job_phase2(U16Job &J) {
     sarpro_hip_ctx *ctx = J.ctx;
     if (!J.clahe()) return SARPRO_HIP_OK;
-    HIPCHK(ctx, ctx->tile_bins.reserve(sizeof(uint64_t) * 64 * 256 * kMaxBands));
+    HIPCHK(ctx, layout::reserve_tile_bins(ctx));
     TileBinHistArgs ta{};
     for (int b = 0; b < J.nbands; ++b) {
-        uint8_t *stage = ctx->h_upload.as<uint8_t>() + (size_t)b * 65536;
+        uint8_t *stage = ctx->h_upload.as<uint8_t>() + layout::kUploadOffLuts + (size_t)b * 65536;
         for (int i = 0; i < 65536; ++i) stage[i] = (uint8_t)J.lut[b].full[i];
-        HIPCHK(ctx, hipMemcpyAsync(ctx->luts.as<uint8_t>() + (size_t)b * 131072, stage, 65536, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(layout::lut_of(ctx, b), stage, 65536, hipMemcpyHostToDevice, ctx->stream));
         ta.tile_hist[b] = tile_hist_of(ctx, b, kTiles * kTiles);
-        ta.binlut[b] = ctx->luts.as<uint8_t>() + (size_t)b * 131072;
-        ta.out[b] = ctx->tile_bins.as<unsigned long long>() + (size_t)b * 64 * 256;
+        ta.binlut[b] = layout::lut_of(ctx, b);
+        ta.out[b] = layout::tile_bins_of(ctx, b);
     }
     KernelTimer t(ctx, "tile_bin_hist");
     HIPCHK(ctx, launch_tile_bin_hist(ta, kTiles * kTiles, J.nbands, ctx->stream));
@@ -222,18 +218,19 @@ int ensure_levels(U16Job &J) {
 int job_phase3(U16Job &J, void *const d_out[kMaxBands], size_t out_pitch) {
     sarpro_hip_ctx *ctx = J.ctx;
     const bool u8o = J.u8_out();
-    HIPCHK(ctx, ctx->level_hist.reserve(sizeof(uint64_t) * 256 * kMaxBands));
+    HIPCHK(ctx, layout::reserve_level_hist(ctx));
     if (J.clahe()) {
         // CDFs from the (reduced) tile histograms
-        const size_t tb_bytes = sizeof(uint64_t) * 64 * 256 * (size_t)J.nbands;
-        HIPCHK(ctx, ctx->h_small.reserve(sizeof(uint64_t) * 64 * 256 * kMaxBands + sizeof(uint64_t) * 256 * kMaxBands));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->h_small.p, ctx->tile_bins.p, tb_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        const size_t tb_bytes = sizeof(uint64_t) * layout::kTileBinCount * (size_t)J.nbands;
+        HIPCHK(ctx, layout::reserve_h_small(ctx));
+        uint64_t *h_tb = reinterpret_cast<uint64_t *>(ctx->h_small.as<uint8_t>() + layout::kSmallOffTileBins);
+        HIPCHK(ctx, hipMemcpyAsync(h_tb, ctx->tile_bins.p, tb_bytes, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        HIPCHK(ctx, ctx->cdfs.reserve(sizeof(double) * 64 * 256 * kMaxBands));
-        double *h_cdfs = reinterpret_cast<double *>(ctx->h_upload.as<uint8_t>() + 2 * 131072);
+        HIPCHK(ctx, layout::reserve_cdfs(ctx));
+        double *h_cdfs = reinterpret_cast<double *>(ctx->h_upload.as<uint8_t>() + layout::kUploadOffCdfs);
         for (int b = 0; b < J.nbands; ++b)
-            RETCHK(clahe_cdfs(ctx->h_small.as<uint64_t>() + (size_t)b * 64 * 256, J.rows_total, J.cols, h_cdfs + (size_t)b * 64 * 256));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->cdfs.p, h_cdfs, sizeof(double) * 64 * 256 * (size_t)J.nbands, hipMemcpyHostToDevice, ctx->stream));
+            RETCHK(clahe_cdfs(h_tb + (size_t)b * layout::kTileBinCount, J.rows_total, J.cols, h_cdfs + (size_t)b * layout::kTileBinCount));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->cdfs.p, h_cdfs, sizeof(double) * layout::kTileBinCount * (size_t)J.nbands, hipMemcpyHostToDevice, ctx->stream));
 
         ClaheApplyArgs a{};
         const bool direct = !J.synrgb && d_out[0] != nullptr; // single band: write the caller's raster
@@ -242,12 +239,12 @@ int job_phase3(U16Job &J, void *const d_out[kMaxBands], size_t out_pitch) {
         for (int b = 0; b < J.nbands; ++b) {
             a.in[b] = J.d_in[b];
             a.out[b] = direct ? d_out[b] : (void *)J.d_levels[b];
-            a.cdfs[b] = ctx->cdfs.as<double>() + (size_t)b * 64 * 256;
-            a.binlut[b] = ctx->luts.as<uint8_t>() + (size_t)b * 131072;
+            a.cdfs[b] = layout::cdfs_of(ctx, b);
+            a.binlut[b] = layout::lut_of(ctx, b);
             a.win_lo[b] = J.lut[b].win_lo;
             a.win_hi[b] = J.lut[b].win_hi;
             win_max = std::max<size_t>(win_max, J.lut[b].win_hi - J.lut[b].win_lo + 1);
-            a.level_hist[b] = u8o ? ctx->level_hist.as<unsigned long long>() + (size_t)b * 256 : nullptr;
+            a.level_hist[b] = u8o ? layout::level_hist_of(ctx, b) : nullptr;
         }
         a.in_pitch = J.in_pitch;
         a.out_pitch = direct ? out_pitch : J.lvl_pitch;
@@ -257,7 +254,7 @@ int job_phase3(U16Job &J, void *const d_out[kMaxBands], size_t out_pitch) {
         a.col_w = J.plan->d_col_w.as<RowWeight>();
         a.row_off = (int32_t)J.row0;
         a.max_val = u8o ? 255.0 : 65535.0;
-        if (u8o) HIPCHK(ctx, hipMemsetAsync(ctx->level_hist.p, 0, sizeof(uint64_t) * 256 * kMaxBands, ctx->stream));
+        if (u8o) HIPCHK(ctx, hipMemsetAsync(ctx->level_hist.p, 0, layout::kLevelHistBytes, ctx->stream));
         const bool vec = J.vec && a.out_pitch % 8 == 0 && ptr_aligned16(a.out[0]) && (J.nbands < 2 || ptr_aligned16(a.out[1]));
         if (vec != J.vec) return fail(ctx, SARPRO_HIP_ERR_INVALID_ARG, "output raster must be 16-byte aligned with pitch % 8 == 0 when the input is");
         if (J.vec && u8o && clahe_apply_spec_ok(a, J.nbands) && !ctx->attrs.on(A_NO_SPEC)) {
@@ -279,7 +276,7 @@ int job_phase3(U16Job &J, void *const d_out[kMaxBands], size_t out_pitch) {
     // percentile strategies: the level histogram is known on the host already; publish it on the
     // device too so the stripe protocol reduces the same buffer in both modes
     if (u8o) {
-        uint64_t *stage = reinterpret_cast<uint64_t *>(ctx->h_upload.as<uint8_t>() + 2 * 131072);
+        uint64_t *stage = reinterpret_cast<uint64_t *>(ctx->h_upload.as<uint8_t>() + layout::kUploadOffLevelHist);
         for (int b = 0; b < J.nbands; ++b) std::memcpy(stage + (size_t)b * 256, J.level_hist_h[b], sizeof(uint64_t) * 256);
         HIPCHK(ctx, hipMemcpyAsync(ctx->level_hist.p, stage, sizeof(uint64_t) * 256 * (size_t)J.nbands, hipMemcpyHostToDevice, ctx->stream));
     }
@@ -295,8 +292,8 @@ int job_phase4(U16Job &J, void *const d_out[kMaxBands], size_t out_pitch, uint8_
     const uint32_t rows = (uint32_t)J.rows_local, cols = (uint32_t)J.cols;
 
     if (u8o && (J.clahe() || level_hist_reduced_on_device)) {
-        HIPCHK(ctx, ctx->h_small.reserve(sizeof(uint64_t) * 64 * 256 * kMaxBands + sizeof(uint64_t) * 256 * kMaxBands));
-        uint64_t *h = ctx->h_small.as<uint64_t>() + 64 * 256 * kMaxBands;
+        HIPCHK(ctx, layout::reserve_h_small(ctx));
+        uint64_t *h = reinterpret_cast<uint64_t *>(ctx->h_small.as<uint8_t>() + layout::kSmallOffLevelHist);
         HIPCHK(ctx, hipMemcpyAsync(h, ctx->level_hist.p, sizeof(uint64_t) * 256 * (size_t)J.nbands, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         for (int b = 0; b < J.nbands; ++b) {
@@ -334,11 +331,11 @@ int job_phase4(U16Job &J, void *const d_out[kMaxBands], size_t out_pitch, uint8_
             a.win_lo = J.lut[b].win_lo; a.win_hi = J.lut[b].win_hi;
             const size_t esz = u8o ? 1 : 2;
             a.lut_in_lds = (size_t)(a.win_hi - a.win_lo + 1) * esz <= kLutLdsMaxBytes;
-            uint8_t *stage = up + (size_t)b * 131072;
+            uint8_t *stage = up + layout::kUploadOffLuts + (size_t)b * layout::kLutBandStride;
             if (u8o) for (int i = 0; i < 65536; ++i) stage[i] = J.resc[b][J.lut[b].full[i] & 0xFF];
-            else std::memcpy(stage, J.lut[b].full.data(), 131072);
+            else std::memcpy(stage, J.lut[b].full.data(), 65536 * sizeof(uint16_t));
             if (u8o) stage[0] = J.resc[b][0];
-            void *d_lut = ctx->luts.as<uint8_t>() + (size_t)b * 131072;
+            void *d_lut = layout::lut_of(ctx, b);
             HIPCHK(ctx, hipMemcpyAsync(d_lut, stage, 65536 * esz, hipMemcpyHostToDevice, ctx->stream));
             a.lut = d_lut;
             if (fused) continue; // the tables are consumed by the fused pass below
@@ -349,9 +346,9 @@ int job_phase4(U16Job &J, void *const d_out[kMaxBands], size_t out_pitch, uint8_
     }
     if (!J.synrgb) {
         if (J.clahe() && u8o && !J.resc_identity[0]) { // rare: CLAHE levels did not span 0..255
-            HIPCHK(ctx, ctx->tables.reserve(66048));
-            std::memcpy(up, J.resc[0], 256);
-            HIPCHK(ctx, hipMemcpyAsync(ctx->tables.p, up, 256, hipMemcpyHostToDevice, ctx->stream));
+            HIPCHK(ctx, layout::reserve_tables(ctx));
+            std::memcpy(up + layout::kUploadOffFlatTables, J.resc[0], 256);
+            HIPCHK(ctx, hipMemcpyAsync(ctx->tables.p, up + layout::kUploadOffFlatTables, 256, hipMemcpyHostToDevice, ctx->stream));
             KernelTimer t(ctx, "remap_u8");
             HIPCHK(ctx, launch_remap_u8(reinterpret_cast<uint8_t *>(d_out[0]), out_pitch, rows, cols, ctx->tables.as<uint8_t>(), ctx->stream));
         }
@@ -365,31 +362,21 @@ int job_phase4(U16Job &J, void *const d_out[kMaxBands], size_t out_pitch, uint8_
     std::memset(combined, 0, sizeof(combined));
     for (int b = 0; b < 2; ++b)
         for (int i = 0; i < 256; ++i) combined[J.resc[b][i]] += J.level_hist_h[b][i];
-    std::vector<uint8_t> luts(66048), tables(66048);
-    const bool suppressed = J.strategy == SARPRO_STRATEGY_TAMED || J.strategy == SARPRO_STRATEGY_CLAHE;
-    if (suppressed) {
-        J.floor_with_cushion = synrgb_floor_from_hist(combined, (uint64_t)J.rows_total * J.cols);
-        synrgb_luts_suppressed(J.floor_with_cushion, luts.data());
-    } else {
-        J.floor_with_cushion = -1;
-        synrgb_luts_default(luts.data());
-    }
-    uint8_t ident[256];
-    for (int i = 0; i < 256; ++i) ident[i] = (uint8_t)i;
     // CLAHE: the compose kernel reads LEVELS, so the rescale is folded into the tables.
     // Percentile strategies: the table-apply pass already wrote final u8 values.
-    const uint8_t *r1 = J.clahe() ? J.resc[0] : ident, *r2 = J.clahe() ? J.resc[1] : ident;
-    fold_compose_tables(luts.data(), J.floor_with_cushion, r1, r2, tables.data());
-    HIPCHK(ctx, ctx->tables.reserve(66048 + 512));
-    uint8_t *tstage = up + 2 * 131072 + 2 * 64 * 256 * 8;
-    std::memcpy(tstage, tables.data(), 66048);
-    HIPCHK(ctx, hipMemcpyAsync(ctx->tables.p, tstage, 66048, hipMemcpyHostToDevice, ctx->stream));
+    std::vector<uint8_t> tables(layout::kComposeBytes);
+    J.floor_with_cushion = build_compose_tables(J.strategy, combined, (uint64_t)J.rows_total * J.cols, J.clahe() ? J.resc[0] : nullptr,
+                                                J.clahe() ? J.resc[1] : nullptr, tables.data());
+    HIPCHK(ctx, layout::reserve_tables(ctx));
+    uint8_t *tstage = up + layout::kUploadOffTables;
+    std::memcpy(tstage, tables.data(), layout::kComposeBytes);
+    HIPCHK(ctx, hipMemcpyAsync(ctx->tables.p, tstage, layout::kComposeBytes, hipMemcpyHostToDevice, ctx->stream));
 
     if (fused) {
         LutComposeArgs f{};
         for (int b = 0; b < 2; ++b) {
             f.in[b] = J.d_in[b];
-            f.lut[b] = ctx->luts.as<uint8_t>() + (size_t)b * 131072;
+            f.lut[b] = layout::lut_of(ctx, b);
             f.win_hi[b] = J.lut[b].win_hi;
         }
         f.rgb = d_rgb; f.in_pitch = J.in_pitch; f.rgb_pitch_px = rgb_pitch_px; f.rows = rows; f.cols = cols;
@@ -421,11 +408,10 @@ int job_phase4(U16Job &J, void *const d_out[kMaxBands], size_t out_pitch, uint8_
             if (!d_out[b]) continue;
             HIPCHK(ctx, hipMemcpy2DAsync(d_out[b], out_pitch, J.d_levels[b], J.lvl_pitch, cols, rows, hipMemcpyDeviceToDevice, ctx->stream));
             if (!J.resc_identity[b]) {
-                uint8_t *m = tstage + 66048 + (size_t)b * 256;
+                uint8_t *m = tstage + layout::kTablesOffMaps + (size_t)b * 256, *d_map = ctx->tables.as<uint8_t>() + layout::kTablesOffMaps + (size_t)b * 256;
                 std::memcpy(m, J.resc[b], 256);
-                HIPCHK(ctx, hipMemcpyAsync(ctx->tables.as<uint8_t>() + 66048 + (size_t)b * 256, m, 256, hipMemcpyHostToDevice, ctx->stream));
-                HIPCHK(ctx, launch_remap_u8(reinterpret_cast<uint8_t *>(d_out[b]), out_pitch, rows, cols,
-                                            ctx->tables.as<uint8_t>() + 66048 + (size_t)b * 256, ctx->stream));
+                HIPCHK(ctx, hipMemcpyAsync(d_map, m, 256, hipMemcpyHostToDevice, ctx->stream));
+                HIPCHK(ctx, launch_remap_u8(reinterpret_cast<uint8_t *>(d_out[b]), out_pitch, rows, cols, d_map, ctx->stream));
             }
         }
     }

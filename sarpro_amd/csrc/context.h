@@ -223,7 +223,7 @@ struct sarpro_hip_ctx {
     sarpro::DevBuf level_hist;                   // u64 [2][256]
     sarpro::DevBuf spec_dump;                    // kSpecDumpBytes: write-only scratch of the speculative apply kernel
     sarpro::DevBuf hist_flags;                   // u32 [2]: band whose partial level histogram had to be recounted
-    sarpro::DevBuf tables;                       // compose tables 66048 B
+    sarpro::DevBuf tables;                       // compose tables | per-band maps | blue factors by level (workspace_layout.h)
     sarpro::DevBuf spec_state;                   // ChainSpecState of the speculative CLAHE chain (chain_kernels.h)
     int cu_count = 0;                            // compute units of the device (grid of the persistent piece kernels)
     sarpro::DevBuf levels[sarpro::kMaxBands];    // u8 level rasters (intermediate)
@@ -286,7 +286,7 @@ struct sarpro_hip_ctx {
     hipEvent_t pipe_record_after_fused = nullptr; // ... and records this one behind itself
     hipEvent_t pipe_wait_before_hist = nullptr;   // PIPE_ORDER = 2: the scene's histogram pass waits for this event (the previous scene's fused pass is about to start) ...
     hipEvent_t pipe_record_before_fused = nullptr; // ... and the scene records this one in front of its own fused pass
-    // PIPE_ORDER = 3 (the default of the resident batch): the two sweeps of all lanes in ONE order -- H(i + 1), F(i), H(i + 2), F(i + 1), ...
+    // PIPE_ORDER = 3 (the resident batch's default is 0, the free run: pipeline.cpp): the two sweeps of all lanes in ONE order -- H(i + 1), F(i), H(i + 2), F(i + 1), ...
     hipEvent_t pipe_record_after_hist = nullptr;  // the scene records this one behind its histogram sweep
     bool pipe_defer = false;                      // the chain stops in front of its fused pass and parks the rest ...
     std::function<int()> pipe_deferred;           // ... here: the batch driver calls it once the NEXT scene's sweep is enqueued

@@ -12,6 +12,7 @@
 #include "chain_kernels.h"
 #include "f32_kernels.h"
 #include "internal.h"
+#include "workspace_layout.h"
 
 using namespace sarpro;
 
@@ -509,8 +510,8 @@ int f32_phase_a(F32Band &B) {
     B.local.min_v = INFINITY; B.local.max_v = -INFINITY;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, ctx->f32ws.reserve(kWsBytes));
-    HIPCHK(ctx, ctx->h_small.reserve(sizeof(uint64_t) * 64 * 256 * kMaxBands + sizeof(uint64_t) * 256 * kMaxBands + 64 * 1024 + 65536 * 16));
-    HIPCHK(ctx, ctx->h_upload.reserve(2 * 131072 + 2 * 64 * 256 * 8 + 66048 + 1024));
+    HIPCHK(ctx, layout::reserve_h_small(ctx, true));
+    HIPCHK(ctx, layout::reserve_h_upload(ctx));
     B.vec = B.pol.op < 0 ? (B.in_pitch % 4 == 0 && aligned16(B.d_in))
                          : (B.pol.pitch % 4 == 0 && aligned16(B.pol.a) && aligned16(B.pol.b));
     B.t_valid = valid_threshold_f32();
@@ -554,17 +555,17 @@ int f32_phase_a(F32Band &B) {
             HIPCHK(ctx, launch_f32_hist4096_direct(B.d_in, B.in_pitch, rows, cols, B.t_valid, B.vec, d_part, pgrid, d_hist, d_qn, ctx->f32zone.as<uint4>(),
                                                    direct_queue_cap(ctx), ctx->stream, B.pol));
         }
-        uint8_t *h = mail ? ctx->mailbox.as<uint8_t>() + kMailBigOff + 64 * 1024 : ctx->h_small.as<uint8_t>() + 64 * 1024; // behind the partials (<= 2048 x 32 B)
+        uint8_t *h = (mail ? ctx->mailbox.as<uint8_t>() + kMailBigOff : ctx->h_small.as<uint8_t>()) + layout::kSmallOffF32Direct; // behind the partials (<= 2048 x 32 B)
         B.direct_host = h;
         if (mail) {
             pg.src[1] = d_hist; pg.dst[1] = h; pg.bytes[1] = sizeof(uint64_t) * 4096;
-            pg.src[2] = d_qn; pg.dst[2] = h + 32768; pg.bytes[2] = 4;
-            pg.src[3] = ctx->f32zone.p; pg.dst[3] = h + 32768 + 64; pg.bytes[3] = kQueueHead * 16; // usually all of them
+            pg.src[2] = d_qn; pg.dst[2] = h + layout::kSmallF32DirectCount; pg.bytes[2] = 4;
+            pg.src[3] = ctx->f32zone.p; pg.dst[3] = h + layout::kSmallF32DirectQueue; pg.bytes[3] = kQueueHead * 16; // usually all of them
             pg.n = 4;
         } else {
             HIPCHK(ctx, hipMemcpyAsync(h, d_hist, sizeof(uint64_t) * 4096, hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHK(ctx, hipMemcpyAsync(h + 32768, d_qn, 4, hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHK(ctx, hipMemcpyAsync(h + 32768 + 64, ctx->f32zone.p, (size_t)kQueueHead * 16, hipMemcpyDeviceToHost, ctx->stream)); // usually all of them
+            HIPCHK(ctx, hipMemcpyAsync(h + layout::kSmallF32DirectCount, d_qn, 4, hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(ctx, hipMemcpyAsync(h + layout::kSmallF32DirectQueue, ctx->f32zone.p, (size_t)kQueueHead * 16, hipMemcpyDeviceToHost, ctx->stream)); // usually all of them
         }
     }
     if (mail) {
@@ -614,7 +615,7 @@ int f32_phase_c(F32Band &B) {
     unsigned long long *d_tile_bins = reinterpret_cast<unsigned long long *>(ws + kOffTileBins);
     unsigned long long *d_level_hist = reinterpret_cast<unsigned long long *>(ws + kOffLevelHist);
     Prep pr;
-    if (B.clahe) pr.zero(d_tile_bins, sizeof(uint64_t) * 64 * 256);
+    if (B.clahe) pr.zero(d_tile_bins, sizeof(uint64_t) * layout::kTileBinCount);
     pr.zero(d_level_hist, sizeof(uint64_t) * 256);
     pr.zero(ws + kOffZoneCounts, 4); // the level pass's queue counter (phase d; the zone counts were read before this phase)
     if (B.empty || !B.have_stats || !B.clahe || B.rows == 0 || B.cols == 0) { RETCHK(prep_run(ctx, pr)); pr = Prep(); }
@@ -770,11 +771,11 @@ int f32_phase_d(F32Band &B) {
     double *d_cdfs = reinterpret_cast<double *>(ws + kOffCdfs);
     if (ctx->attrs.on(A_F32_HOST_CDFS)) { // the host twin of the kernel below (cross-check switch)
         uint64_t *h_tb = ctx->h_small.as<uint64_t>();
-        HIPCHK(ctx, hipMemcpyAsync(h_tb, ws + kOffTileBins, sizeof(uint64_t) * 64 * 256, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(h_tb, ws + kOffTileBins, sizeof(uint64_t) * layout::kTileBinCount, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         double *h_cdfs = reinterpret_cast<double *>(ctx->h_upload.as<uint8_t>() + 4096);
         RETCHK(clahe_cdfs(h_tb, B.rows_total, B.cols, h_cdfs));
-        HIPCHK(ctx, hipMemcpyAsync(d_cdfs, h_cdfs, sizeof(double) * 64 * 256, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(d_cdfs, h_cdfs, sizeof(double) * layout::kTileBinCount, hipMemcpyHostToDevice, ctx->stream));
     } else { // clip / redistribute / CDF per tile on the device (chain_kernels.hip, the u16 chain's kernel): no host turn
         KernelTimer t(ctx, "chain_cdfs");
         HIPCHK(ctx, launch_chain_cdfs(reinterpret_cast<const unsigned long long *>(ws + kOffTileBins), d_cdfs, (uint32_t)B.rows_total, (uint32_t)B.cols, 1,
@@ -841,16 +842,16 @@ int f32_direct_stats(F32Band &B) {
     uint8_t *h = B.direct_host; // where phase a had the bins, the queue count and the queue's head delivered
     uint64_t *h_hist = reinterpret_cast<uint64_t *>(h);
     uint32_t nq = 0;
-    std::memcpy(&nq, h + 32768, 4);
+    std::memcpy(&nq, h + layout::kSmallF32DirectCount, 4);
     if (nq > direct_queue_cap(ctx)) { B.direct = false; return SARPRO_HIP_OK; }
     B.mean = G.sum_db / (double)G.count;
     const double var = G.sumsq_db / (double)G.count - B.mean * B.mean;
     B.std_db = G.count > 1 ? std::sqrt(std::fmax(var, 0.0)) : 0.0;
     B.min_db = db_of_f32(G.min_v); B.max_db = db_of_f32(G.max_v);
     if (nq && !(std::fabs(B.max_db - B.min_db) < 2.220446049250313e-16)) {
-        uint32_t *h_e = reinterpret_cast<uint32_t *>(h + 32768 + 64);
+        uint32_t *h_e = reinterpret_cast<uint32_t *>(h + layout::kSmallF32DirectQueue);
         if (nq > kQueueHead) { // (the first kQueueHead entries came with the count; all of them: into the pinned buffer, the mailbox has no room)
-            h_e = reinterpret_cast<uint32_t *>(ctx->h_small.as<uint8_t>() + 64 * 1024 + 32768 + 64);
+            h_e = reinterpret_cast<uint32_t *>(ctx->h_small.as<uint8_t>() + layout::kSmallOffF32Direct + layout::kSmallF32DirectQueue);
             HIPCHK(ctx, hipMemcpyAsync(h_e, ctx->f32zone.p, (size_t)nq * 16, hipMemcpyDeviceToHost, ctx->stream));
             HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         }
@@ -1034,7 +1035,7 @@ extern "C" int sarpro_hip_stripe_f32_phase3(sarpro_hip_stripe_f32 *s, uint64_t *
     if (!s || !d_buf || !count || s->phase != 2) return SARPRO_HIP_ERR_INVALID_ARG;
     RETCHK(f32_phase_c(s->B));
     s->phase = 3;
-    return stripe_f32_buf(s, kOffTileBins, 64 * 256, s->B.clahe, d_buf, count);
+    return stripe_f32_buf(s, kOffTileBins, layout::kTileBinCount, s->B.clahe, d_buf, count);
 }
 
 extern "C" int sarpro_hip_stripe_f32_phase4(sarpro_hip_stripe_f32 *s, uint64_t **d_buf, size_t *count) {
@@ -1065,7 +1066,7 @@ static int stripe_f32_run(sarpro_hip_stripe_f32 *s, sarpro_hip_stats *stats_out)
     sarpro_hip_ctx *ctx = B.ctx;
     if (!ctx->comm && !ctx->local_group) return fail(ctx, SARPRO_HIP_ERR_INVALID_ARG, "communicator not initialised");
     const int n = ctx->comm_nranks, me = ctx->comm_rank;
-    if (n > 1024) return fail(ctx, SARPRO_HIP_ERR_INVALID_ARG, "more than 1024 ranks");
+    if ((size_t)n > layout::kSmallF32MaxRanks) return fail(ctx, SARPRO_HIP_ERR_INVALID_ARG, "more than 1024 ranks");
     // A rank that fails locally (bad pitch, a HIP error in its first pass, no plan) must not leave its peers waiting in a
     // collective: its status travels WITH the first reduction (one more word behind the gathered partials) and in a one-word
     // reduction after the phase that builds plans and tables; every rank then returns an error together.  A failure between later
@@ -1076,7 +1077,7 @@ static int stripe_f32_run(sarpro_hip_stripe_f32 *s, sarpro_hip_stats *stats_out)
     static_assert(sizeof(sarpro_hip_f32_partial) == 32, "partial = 4 words");
     HIPCHK(ctx, ctx->f32ws.reserve(kWsBytes)); // (phase a may have failed before it did)
     uint64_t *d_g = reinterpret_cast<uint64_t *>(ctx->f32ws.as<uint8_t>() + kOffPartials);
-    HIPCHK(ctx, ctx->h_small.reserve(sizeof(uint64_t) * 64 * 256 * kMaxBands + sizeof(uint64_t) * 256 * kMaxBands));
+    HIPCHK(ctx, layout::reserve_h_small(ctx)); // (the gathered partials of kSmallF32MaxRanks ranks fit: workspace_layout.h)
     uint64_t *h_g = ctx->h_small.as<uint64_t>();
     HIPCHK(ctx, hipMemsetAsync(d_g, 0, 32 * (size_t)n + 8, ctx->stream));
     if (rc_a == SARPRO_HIP_OK) std::memcpy(h_g, &B.local, 32); else std::memset(h_g, 0, 32);
@@ -1105,7 +1106,7 @@ static int stripe_f32_run(sarpro_hip_stripe_f32 *s, sarpro_hip_stats *stats_out)
         if (rc_c != SARPRO_HIP_OK) return rc_c;
         if (h_g[0] != 0) return fail(ctx, SARPRO_HIP_ERR_RCCL, "another rank failed while building its plan and tables; every rank returns");
     }
-    if (B.clahe) RETCHK(comm_allreduce_sum_u64_async(ctx, reinterpret_cast<uint64_t *>(ws + kOffTileBins), 64 * 256));
+    if (B.clahe) RETCHK(comm_allreduce_sum_u64_async(ctx, reinterpret_cast<uint64_t *>(ws + kOffTileBins), layout::kTileBinCount));
     RETCHK(f32_phase_d(B));
     if (B.u8o) RETCHK(comm_allreduce_sum_u64_async(ctx, reinterpret_cast<uint64_t *>(ws + kOffLevelHist), 256));
     RETCHK(f32_phase_e(B));
@@ -1384,28 +1385,19 @@ static int dualpol_f32_impl(sarpro_hip_ctx *ctx, const DualF32Src &src, size_t r
         return SARPRO_HIP_OK;
     }
     const size_t lpitch = round_up(std::max<size_t>(cols, 1), 64);
-    std::vector<uint8_t> luts(66048), tables(66048);
-    int fwc = -1;
-    if (strategy == SARPRO_STRATEGY_TAMED || strategy == SARPRO_STRATEGY_CLAHE) { // synthetic_rgb.rs:188-194
-        fwc = synrgb_floor_from_hist(combined, (uint64_t)rows * cols);
-        synrgb_luts_suppressed(fwc, luts.data());
-    } else {
-        synrgb_luts_default(luts.data());
-    }
-    uint8_t ident[256];
-    for (int i = 0; i < 256; ++i) ident[i] = (uint8_t)i;
-    fold_compose_tables(luts.data(), fwc, ident, ident, tables.data());
-    HIPCHK(ctx, ctx->tables.reserve(66048 + 512));
+    std::vector<uint8_t> tables(layout::kComposeBytes);
+    build_compose_tables(strategy, combined, (uint64_t)rows * cols, nullptr, nullptr, tables.data());
+    HIPCHK(ctx, layout::reserve_tables(ctx));
     if (mail_enabled(ctx) && mail_open(ctx) == SARPRO_HIP_OK) { // the tables through the mailbox's big-payload area (both bands' turns are over): a kernel, not a copy command
         uint8_t *tstage = ctx->mailbox.as<uint8_t>() + kMailBigOff;
-        std::memcpy(tstage, tables.data(), 66048);
+        std::memcpy(tstage, tables.data(), layout::kComposeBytes);
         Prep pr;
-        pr.upload(tstage, ctx->tables.p, 66048);
+        pr.upload(tstage, ctx->tables.p, layout::kComposeBytes);
         RETCHK(prep_run(ctx, pr));
     } else {
-        uint8_t *tstage = ctx->h_upload.as<uint8_t>();
-        std::memcpy(tstage, tables.data(), 66048);
-        HIPCHK(ctx, hipMemcpyAsync(ctx->tables.p, tstage, 66048, hipMemcpyHostToDevice, ctx->stream));
+        uint8_t *tstage = ctx->h_upload.as<uint8_t>() + layout::kUploadOffFlatTables;
+        std::memcpy(tstage, tables.data(), layout::kComposeBytes);
+        HIPCHK(ctx, hipMemcpyAsync(ctx->tables.p, tstage, layout::kComposeBytes, hipMemcpyHostToDevice, ctx->stream));
     }
     ComposeArgs c{};
     c.b1 = ctx->levels[0].as<uint8_t>(); c.b2 = ctx->levels[1].as<uint8_t>(); c.in_pitch = lpitch;

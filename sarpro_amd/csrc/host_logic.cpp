@@ -556,6 +556,26 @@ void fold_compose_tables(const uint8_t *luts, int fwc, const uint8_t *resc1, con
     }
 }
 
+int synrgb_luts_for_strategy(int strategy, const uint64_t *combined_hist256, uint64_t n_per_band, uint8_t *luts) {
+    if (strategy == SARPRO_STRATEGY_TAMED || strategy == SARPRO_STRATEGY_CLAHE) { // synthetic_rgb.rs:188-194
+        const int fwc = synrgb_floor_from_hist(combined_hist256, n_per_band);
+        synrgb_luts_suppressed(fwc, luts);
+        return fwc;
+    }
+    synrgb_luts_default(luts);
+    return -1;
+}
+
+int build_compose_tables(int strategy, const uint64_t *combined_hist256, uint64_t n_per_band, const uint8_t *resc1, const uint8_t *resc2,
+                         uint8_t *tables) {
+    std::vector<uint8_t> luts(66048);
+    const int fwc = synrgb_luts_for_strategy(strategy, combined_hist256, n_per_band, luts.data());
+    uint8_t ident[256];
+    for (int i = 0; i < 256; ++i) ident[i] = (uint8_t)i;
+    fold_compose_tables(luts.data(), fwc, resc1 ? resc1 : ident, resc2 ? resc2 : ident, tables);
+    return fwc;
+}
+
 int stripe_plan(size_t rows, int nranks, size_t *row0, size_t *nrows) {
     if (nranks <= 0) return SARPRO_HIP_ERR_INVALID_ARG;
     for (int k = 0; k < nranks; ++k) {
@@ -616,15 +636,9 @@ int sarpro_hip_host_u8_rescale_lut(unsigned min_level, unsigned max_level, uint8
 int sarpro_hip_host_synrgb_luts(int strategy, const uint64_t combined_hist[256], uint64_t n_per_band,
                                 uint8_t *luts_out, int *floor_out) {
     if (!luts_out || strategy < 0 || strategy > SARPRO_STRATEGY_DEFAULT) return SARPRO_HIP_ERR_INVALID_ARG;
-    if (strategy == SARPRO_STRATEGY_TAMED || strategy == SARPRO_STRATEGY_CLAHE) { // synthetic_rgb.rs:188-194
-        if (!combined_hist) return SARPRO_HIP_ERR_INVALID_ARG;
-        int fwc = synrgb_floor_from_hist(combined_hist, n_per_band);
-        synrgb_luts_suppressed(fwc, luts_out);
-        if (floor_out) *floor_out = fwc;
-    } else {
-        synrgb_luts_default(luts_out);
-        if (floor_out) *floor_out = -1;
-    }
+    if ((strategy == SARPRO_STRATEGY_TAMED || strategy == SARPRO_STRATEGY_CLAHE) && !combined_hist) return SARPRO_HIP_ERR_INVALID_ARG;
+    const int fwc = synrgb_luts_for_strategy(strategy, combined_hist, n_per_band, luts_out);
+    if (floor_out) *floor_out = fwc;
     return SARPRO_HIP_OK;
 }
 

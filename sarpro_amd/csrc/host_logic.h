@@ -81,6 +81,14 @@ void synrgb_luts_suppressed(int floor_with_cushion, uint8_t *luts);
 void fold_compose_tables(const uint8_t *luts, int floor_with_cushion /* -1: none */,
                          const uint8_t *resc1, const uint8_t *resc2, uint8_t *tables);
 
+// The two steps above as the products take them (synthetic_rgb.rs:182-197).  synrgb_luts_for_strategy: Tamed and CLAHE compose with the
+// suppressed variant, its floor from the combined histogram of the final u8 bands (n_per_band pixels each); the others with the default
+// variant, which reads no histogram.  Returns the floor with its cushion, -1 when the variant has none.
+int synrgb_luts_for_strategy(int strategy, const uint64_t *combined_hist256, uint64_t n_per_band, uint8_t *luts);
+// ... and those luts folded with the bands' rescale maps (nullptr: the identity) into the 66048-byte block the compose kernels read
+int build_compose_tables(int strategy, const uint64_t *combined_hist256, uint64_t n_per_band, const uint8_t *resc1, const uint8_t *resc2,
+                         uint8_t *tables);
+
 int stripe_plan(size_t rows, int nranks, size_t *row0, size_t *nrows);
 
 // constant tables the device-resident chain uploads once (chain_kernels.hip)

@@ -8,6 +8,7 @@
 
 #include "internal.h"
 #include "resize_kernels.h"
+#include "workspace_layout.h"
 
 using namespace sarpro;
 
@@ -61,7 +62,7 @@ int get_coeffs(sarpro_hip_ctx *ctx, int slot, uint32_t in_size, uint32_t out_siz
     const size_t kb = c.k.size() * sizeof(int32_t);
     const size_t bytes = n * 8 + kb;
     HIPCHK(ctx, buf.reserve(bytes));
-    HIPCHK(ctx, ctx->h_upload.reserve(std::max<size_t>(bytes, 2 * 131072 + 2 * 64 * 256 * 8 + 66048 + 1024)));
+    HIPCHK(ctx, layout::reserve_h_upload(ctx, bytes));
     uint8_t *h = ctx->h_upload.as<uint8_t>();
     std::memcpy(h, c.start.data(), n * 4);
     std::memcpy(h + n * 4, c.size.data(), n * 4);

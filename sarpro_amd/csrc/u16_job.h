@@ -5,6 +5,7 @@
 #include "context.h"
 #include "host_logic.h"
 #include "internal.h"
+#include "workspace_layout.h"
 
 namespace sarpro {
 

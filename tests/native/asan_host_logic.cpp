@@ -91,6 +91,36 @@ int main() {
         synrgb_luts_suppressed(fwc, luts.data());
         fold_compose_tables(luts.data(), fwc, r1, r2, tables.data());
     }
+    // build_compose_tables against the two steps it replaces, byte for byte: the default tables; the suppressed tables with the scene's
+    // lowest occupied level at 0 .. 40 (the floor search adds its cushion of 3 and caps at 40: every floor it can return); each with
+    // the identity rescale (given, and as nullptr) and two non-identity rescales
+    {
+        uint8_t ident[256], ra[256], rb[256];
+        for (int i = 0; i < 256; ++i) ident[i] = (uint8_t)i;
+        u8_rescale_lut(10, 200, ra);
+        u8_rescale_lut(40, 255, rb);
+        const uint8_t *pairs[4][2] = {{nullptr, nullptr}, {ident, ident}, {ra, rb}, {rb, r2}};
+        std::vector<uint8_t> want(66048), got(66048);
+        for (int strategy : {(int)SARPRO_STRATEGY_STANDARD, (int)SARPRO_STRATEGY_ROBUST, (int)SARPRO_STRATEGY_CLAHE, (int)SARPRO_STRATEGY_TAMED}) {
+            const bool supp = strategy == SARPRO_STRATEGY_CLAHE || strategy == SARPRO_STRATEGY_TAMED;
+            for (int level = 0; level <= (supp ? 40 : 0); ++level) {
+                std::memset(comb, 0, sizeof(comb));
+                comb[level] = 1000; comb[200] = 1000;
+                int fwc = -1;
+                if (supp) { fwc = synrgb_floor_from_hist(comb, 1000); synrgb_luts_suppressed(fwc, luts.data()); }
+                else synrgb_luts_default(luts.data());
+                if (supp && fwc != (level + 3 < 40 ? level + 3 : 40)) std::abort();
+                for (auto &p : pairs) {
+                    fold_compose_tables(luts.data(), fwc, p[0] ? p[0] : ident, p[1] ? p[1] : ident, want.data());
+                    std::memset(got.data(), 0xA5, got.size());
+                    if (build_compose_tables(strategy, comb, 1000, p[0], p[1], got.data()) != fwc) std::abort();
+                    if (std::memcmp(got.data(), want.data(), want.size()) != 0) std::abort();
+                }
+                std::vector<uint8_t> l2(66048);
+                if (synrgb_luts_for_strategy(strategy, comb, 1000, l2.data()) != fwc || l2 != luts) std::abort();
+            }
+        }
+    }
     (void)synrgb_supp_rg_tables(); (void)synrgb_blue_pair_supp(); (void)synrgb_blue_pair_default(); (void)gamma_level_thresholds_u8();
     // resize coefficient tables and dimension rules; stripe plans
     for (uint32_t in : {1u, 2u, 7u, 100u, 2048u, 20000u})
